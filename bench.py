@@ -17,7 +17,18 @@ HBM traffic (src read + dst read + dst write, 24 B per element).  Steps rotate
 over --sets independent buffer sets (default 8 x 512 MiB) so the 256 MiB
 Infinity Cache cannot serve the working set.  Before the timed region the same
 step runs for --warmup steps and then for at least --warmup-ms of wall time,
-so the K timed steps do not start on a cold (clock-ramping) GPU.
+so the K timed steps do not start on a cold (clock-ramping) GPU.  After the
+warm-up every destination is filled again from its seed, so the K timed steps
+start from the same data in every run of the same arguments.
+
+A plain run (no --full) sets up, warms up, times the K steps, writes its
+outputs if --dump-outputs DIR is given and prints the line: metric, value,
+unit, ms_per_step, dtype and the configuration.  --dump-outputs writes what the
+last timed step left in its destination as float64 .npy files (dump_outputs
+below).  Everything else described here -- roofline.achieved and its event-pair
+region, blocking_api, host_inclusive, cpu_baseline, and at N > 1 the C5 extras
+with their cross-GPU checks -- takes runs of its own and is measured only with
+--full.
 
 value = whole-job algorithmic traffic GiB/s = ranks * steps * bytes / max-over-
 ranks wall time of the K timed steps (barrier + synchronize on both sides, no
@@ -113,6 +124,59 @@ def patch_bytes(count):
     for c in count:
         n *= c
     return n
+
+
+# --dump-outputs: at most this many f64 values per array, drawn with DUMP_SEED.  A
+# rank's two arrays then hold at most 7 Mi values (56 MiB), under the 64 MB a dump
+# may take.
+DUMP_PATCH_MAX = 6 << 20
+DUMP_GAP_MAX = 1 << 20
+DUMP_SEED = 0x0D0E5EED
+
+
+def patch_offsets(count, strides):
+    """Offsets, in f64 units from the patch's first byte, of every f64 of a strided
+    patch in the order the descriptor walks it (count[0] contiguous bytes innermost)."""
+    off = np.arange(count[0] // 8, dtype=np.int64)
+    for n, s in zip(count[1:], strides):
+        off = ((np.arange(n, dtype=np.int64) * (s // 8))[:, None] + off[None, :]).reshape(-1)
+    return off
+
+
+def dump_indices(count, strides):
+    """{"patch": ..., "gap": ...}: the f64 offsets into a buffer's span that --dump-outputs
+    writes, in the order it writes them.  patch: the patch's values in descriptor order;
+    gap: the values of the span between the patch's rows.  A set over its limit is a
+    sample at sorted positions drawn with a fixed seed, so every run of the same
+    arguments dumps the same elements."""
+    off = patch_offsets(count, strides)
+    inside = np.zeros(span_bytes(count, strides) // 8, bool)
+    inside[off] = True
+    rng = np.random.default_rng(DUMP_SEED)
+    out = {}
+    for name, idx, limit in (("patch", off, DUMP_PATCH_MAX), ("gap", np.flatnonzero(~inside), DUMP_GAP_MAX)):
+        if idx.size > limit:
+            idx = idx[np.sort(rng.choice(idx.size, limit, replace=False))]
+        out[name] = idx
+    return out
+
+
+def dump_outputs(L, out_dir, rank, size, ptr, count, strides):
+    """--dump-outputs: the buffer the last timed step wrote, as its caller finds it
+    once the step has completed: <dir>/patch.npy and <dir>/gap.npy, the float64
+    values at dump_indices (complex: re, im).  The step must leave the gap alone.
+    The ranks of an N > 1 job write patch.rank<r>.npy and gap.rank<r>.npy.
+    Returns {file name: number of values}."""
+    host = np.empty(span_bytes(count, strides) // 8, np.float64)
+    if L.gaamd_memcpy(host.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(ptr), host.nbytes):
+        raise RuntimeError("--dump-outputs: reading the buffer back failed")
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, idx in dump_indices(count, strides).items():
+        fn = name + (f".rank{rank}" if size > 1 else "") + ".npy"
+        np.save(os.path.join(out_dir, fn), host[idx])
+        written[fn] = int(idx.size)
+    return written
 
 
 # ---------------------------------------------------------------- distributed
@@ -315,9 +379,11 @@ def run_ga(args, dist, exchange=None, steps=None, warmup_ms=None, terminate=True
     elapsed = dist.max(t1 - t0)
     if exchange:
         avg_kernel_s = elapsed / steps   # the work runs on the owners' streams
-    else:
+    elif args.full:
         region_ms, _ = event_region(L, step, steps, nxt + steps)
         avg_kernel_s = dist.max(region_ms / 1e3 / steps)
+    else:
+        avg_kernel_s = None              # the roofline's event-pair region is a run of its own: --full
     routes = {k: v - routes0[k] for k, v in ga_amd.route_counts().items()}
     topology = ga_amd.device_topology()
     if src is not None:
@@ -431,6 +497,17 @@ def run_gpu(args, dist, finalize=True):
     hd.drain()
     ga_amd.sync()
     launch = ga_amd.last_launch()
+    # the warm-up ran for a time, not for a count: fill every destination again from its
+    # seed and restart the rotation at set 0, so the timed steps compute the same values
+    # in every run of the same arguments (what --dump-outputs writes)
+    if seg_dst:
+        L.comex_fence_all(0)
+        L.comex_barrier(0)
+    for i, (_, d, _) in enumerate(sets):
+        ga_amd.fill(segs[i][dist.rank] if seg_dst else d.ptr, dbytes // 8, type_code,
+                    0x5EED0001 + dist.rank + 977 * i)
+    ga_amd.sync()
+    nxt = 0
 
     # value region: barrier + sync on both sides, wall clock, no timing events; no
     # garbage collection inside it (as timeit): a collection pass there is host time
@@ -483,6 +560,17 @@ def run_gpu(args, dist, finalize=True):
     dist.barrier()
     elapsed = dist.max(elapsed)
     nxt += args.steps
+    dumped = None
+    if args.dump_outputs:
+        # the buffer the last timed step wrote: the source side of a get, else this rank's
+        # destination of that step's set (with --exchange, what rank r-1 accumulated into it)
+        last = (nxt - 1) % len(sets)
+        if xfer == "get":
+            dumped = dump_outputs(L, args.dump_outputs, dist.rank, dist.size, sets[last][2], count, sstr)
+        else:
+            dumped = dump_outputs(L, args.dump_outputs, dist.rank, dist.size,
+                                  segs[last][dist.rank] if seg_dst else sets[last][1].ptr, count, dstr)
+        dist.barrier()
     # diagnostics only (BENCH_DIAG_REGIONS=n): n more regions shaped exactly like
     # the value region, to show its spread; `value` stays the first region
     diag = []
@@ -495,12 +583,14 @@ def run_gpu(args, dist, finalize=True):
         diag.append(dict(prof, us_per_step=round(e / args.steps * 1e6, 2)))
     if seg_dst:
         avg_kernel_s = elapsed / args.steps   # the work runs on the owners' streams / progress thread
-    else:
+    elif args.full:
         # roofline: the same K steps again inside per-stream HIP events
         region_ms, nxt = event_region(L, step, args.steps, nxt)
         avg_kernel_s = dist.max(region_ms / 1e3 / args.steps)
+    else:
+        avg_kernel_s = None
     blocking = None
-    if nb and xfer == "acc" and not pipeline and not exchange and not seg_dst:
+    if args.full and nb and xfer == "acc" and not pipeline and not exchange and not seg_dst:
         # the blocking API beside the headline: the same K steps through
         # comex_accs, each returning after its kernel -- a host round trip per step,
         # the call GA's NGA_Acc makes for its last owner (onesided.c:1421-1438)
@@ -555,10 +645,10 @@ def run_gpu(args, dist, finalize=True):
     res = dict(op=op, desc=desc, payload=payload, alg_bytes=alg_bytes, elems=elems, elapsed=elapsed,
                avg_kernel_s=avg_kernel_s, launch=launch, streams=L.gaamd_num_streams(), pipeline=pipeline,
                xfer=xfer, warmup_steps=warmup_steps, region_profile=region_profile, diag_regions=diag,
-               blocking=blocking)
+               blocking=blocking, dumped=dumped)
     for b in packed:
         b.free()
-    if (dist.size == 1 and not args.no_host and xfer == "acc" and not pipeline and not self_packed
+    if (args.full and dist.size == 1 and not args.no_host and xfer == "acc" and not pipeline and not self_packed
             and args.api == "nb"):
         res["host"] = host_inclusive(L, ga_amd, op, count, sstr, dstr, levels, sbytes, dbytes, payload, alg_bytes)
     routes = ga_amd.route_counts()
@@ -1029,7 +1119,16 @@ def main():
     ap.add_argument("--extras-timeout", type=float, default=300.0,
                     help="N>1: seconds the C5 extras may take before the headline line is printed without them")
     ap.add_argument("--verbose", action="store_true", help="progress lines on stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the roofline's event-pair region, the blocking "
+                         "API, the host-inclusive rates, the CPU baseline and, at N>1, the C5 extras and their "
+                         "cross-GPU checks (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one left in its destination buffer to "
+                         "DIR/patch.npy and DIR/gap.npy (float64; a fixed seeded sample of a larger buffer)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload == "C5":
+        ap.error("--dump-outputs covers the comex workloads (" + ", ".join(sorted(WORKLOADS)) + "), not C5")
     if os.environ.get("BENCH_STACK_DUMP_S"):   # diagnostics: where a hung rank is stuck
         import faulthandler
         faulthandler.dump_traceback_later(int(os.environ["BENCH_STACK_DUMP_S"]), exit=False)
@@ -1050,7 +1149,7 @@ def main():
             os.environ[k] = "0"
 
     dist = Dist(args.gpus)
-    extras_on = dist.size > 1 and not args.no_extras and args.workload != "C5"
+    extras_on = args.full and dist.size > 1 and not args.no_extras and args.workload != "C5"
     r = run_gpu(args, dist, finalize=not extras_on)
     # the headline line is complete before the extras start: should the extras (the
     # first cross-GPU exchange of a job) not finish, the watchdog still prints it
@@ -1122,14 +1221,37 @@ class ExtrasWatchdog:
             return True
 
 
+def roofline_entry(r, achieved, traffic):
+    """The line's HBM roofline block, from the event-pair region of a --full run."""
+    return {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "traffic": traffic,
+            "traffic_source": ("profiles/pmc_latest.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
+                               "this workload's kernel (tools/pmc_traffic.py, gfx950 FETCH_SIZE x2), "
+                               "collected in separate profiled runs, not this one") if traffic else None,
+            "kernel_ms_avg": round(r["avg_kernel_s"] * 1e3, 4),
+            "timing": ("HIP events at both ends of every library stream around K more launches of the "
+                       "same step right after the value region (first start to last end) / K"),
+            "frac_kind": ("event-pair figure: an HIP event pair per library stream around K extra launches; "
+                          "the rocprofv3 summaries under profiles/ give the per-launch AverageNs on one "
+                          "stream and the merged busy time per dispatch on the default two streams, which "
+                          "bracket it"),
+            "streams": r["streams"],
+            "rocprof_check": ("consecutive launches overlap on the library streams: compare kernel_ms_avg "
+                              "with the merged busy time per dispatch of the rocprofv3 kernel trace "
+                              "(tools/kernel_union.py), not with AverageNs"
+                              if r["streams"] > 1 else "compare kernel_ms_avg with rocprofv3 AverageNs")}
+
+
 def make_line(args, dist, r, ga_amd):
     n = dist.size
     alg = r["alg_bytes"]
     value = n * args.steps * alg / r["elapsed"] / 2 ** 30
-    achieved = alg / r["avg_kernel_s"] / 1e9
-    traffic = load_traffic(args.workload, alg) if r.get("xfer", "acc") == "acc" else None
+    measured = r["avg_kernel_s"] is not None    # a plain run has no event-pair region: roofline None
+    achieved = alg / r["avg_kernel_s"] / 1e9 if measured else None
+    traffic = load_traffic(args.workload, alg) if measured and r.get("xfer", "acc") == "acc" else None
     cpu = None
-    if not args.no_cpu and n == 1 and args.workload != "C5" and r.get("xfer", "acc") == "acc":
+    if args.full and not args.no_cpu and n == 1 and args.workload != "C5" and r.get("xfer", "acc") == "acc":
         cpu = run_cpu_baseline(args.workload, args.cpu_seconds, args.cpu_threads)
     line = {
         "metric": METRIC,
@@ -1159,35 +1281,21 @@ def make_line(args, dist, r, ga_amd):
                    "kernel": r["launch"]},
         "payload_GiB_per_s": round(value / (3 if r.get("xfer", "acc") == "acc" else 2), 2),
         "hbm_peak_frac": round(value * 2 ** 30 / (dist.size * HBM_PEAK_GBS * 1e9), 4),   # per GPU
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": traffic,
-                     "traffic_source": ("profiles/pmc_latest.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
-                                        "this workload's kernel (tools/pmc_traffic.py, gfx950 FETCH_SIZE x2), "
-                                        "collected in separate profiled runs, not this one") if traffic else None,
-                     "kernel_ms_avg": round(r["avg_kernel_s"] * 1e3, 4),
-                     "timing": ("HIP events at both ends of every library stream around K more launches of the "
-                                "same step right after the value region (first start to last end) / K"),
-                     "frac_kind": ("event-pair figure: an HIP event pair per library stream around K extra launches; "
-                                   "the rocprofv3 summaries under profiles/ give the per-launch AverageNs on one "
-                                   "stream and the merged busy time per dispatch on the default two streams, which "
-                                   "bracket it"),
-                     "streams": r["streams"],
-                     "rocprof_check": ("consecutive launches overlap on the library streams: compare kernel_ms_avg "
-                                       "with the merged busy time per dispatch of the rocprofv3 kernel trace "
-                                       "(tools/kernel_union.py), not with AverageNs"
-                                       if r["streams"] > 1 else "compare kernel_ms_avg with rocprofv3 AverageNs")},
+        "roofline": roofline_entry(r, achieved, traffic) if measured else None,
         "cpu_baseline": cpu,
         "api": ("comex_nbaccs per step, handles waited 64 back + comex_wait_all" if args.api == "nb"
                 else "comex_accs per step (blocking: returns after its kernel)"),
     }
+    line["full"] = args.full   # False: a plain run, only what the headline figure needs
+    if r.get("dumped"):
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "f64_values": r["dumped"]}
     line["hip_runtime"] = ga_amd.lib().gaamd_hip_runtime().decode()
     topo = r.get("topology")
     if n > 1 and topo:
         # how the ranks sat on the node's GPUs (a one-GPU rehearsal must not
         # read as an xGMI run), the C5 entries say the same per measurement
         line["topology"] = dict(topo, ranks=n)
-        if topo["ranks_on_gpu"] > 1:
+        if topo["ranks_on_gpu"] > 1 and measured:
             line["roofline"]["note"] = (f"{topo['ranks_on_gpu']} ranks share each GPU: a rank's kernel time "
                                         "includes the other ranks' traffic on the same HBM")
     if n > 1:
@@ -1202,9 +1310,10 @@ def make_line(args, dist, r, ga_amd):
         line["metric"] = f"GiB/s device-resident strided f64 {r['xfer']} (comex_{r['xfer']}s), not the headline metric"
         line["config"]["step"] = f"comex_{r['xfer']}s of the patch; algorithmic bytes = 2 x payload (read + write)"
     if r.get("pipeline"):
+        line["config"]["step"] = "gaamd_pack + gaamd_unpack_acc on one stream (pack-buffer traffic not credited in value)"
+    if r.get("pipeline") and measured:
         # two kernels per step on one stream: pack moves 2x payload, unpack-acc 3x
         moved = 5 * r["payload"]
-        line["config"]["step"] = "gaamd_pack + gaamd_unpack_acc on one stream (pack-buffer traffic not credited in value)"
         line["roofline"]["achieved"] = round(moved / r["avg_kernel_s"] / 1e9, 1)
         line["roofline"]["frac"] = round(moved / r["avg_kernel_s"] / 1e9 / HBM_PEAK_GBS, 4)
         line["roofline"]["traffic"] = None

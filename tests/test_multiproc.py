@@ -503,7 +503,8 @@ def test_bench_two_ranks_exchange_exact():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4",
+                        "--warmup", "1",
                         "--warmup-ms", "0", "--no-cpu", "--ga-dims", "8192", "--c5-steps", "2"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -525,7 +526,8 @@ def test_bench_extras_watchdog_keeps_headline():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4",
+                        "--warmup", "1",
                         "--warmup-ms", "0", "--no-cpu", "--ga-dims", "8192", "--c5-steps", "2",
                         "--extras-timeout", "0.05"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)

@@ -8,5 +8,7 @@ timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_ou
 echo smoke ok
 bash tools/evidence.sh r01
 echo evidence ok
-timeout -k 10 150 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29543 bench.py --gpus 2 --steps 100 --warmup 10 > gpurun_out/bench_H_2ranks.json 2> gpurun_out/bench_H_2ranks.err
+REHEARSAL=${REHEARSAL:-bench_out}
+mkdir -p "$REHEARSAL"
+timeout -k 10 150 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29543 bench.py --full --gpus 2 --steps 100 --warmup 10 > "$REHEARSAL/bench_H_2ranks.json" 2> "$REHEARSAL/bench_H_2ranks.err"
 echo rehearsal ok

@@ -27,7 +27,7 @@ DRIVER = "python3 bench.py --gpus 1 --steps 20 --warmup 5"
 def _n_proxy(n, port):
     # the driver's N > 1 shape on this box's one GPU, every peer treated as another GPU
     return (f"env COMEX_AMD_PEER_LOADS=all python3 -m torch.distributed.run --nnodes=1 --nproc-per-node {n} "
-            f"--master-addr 127.0.0.1 --master-port {port} bench.py --gpus {n} --steps 20 --warmup 5 --no-cpu")
+            f"--master-addr 127.0.0.1 --master-port {port} bench.py --full --gpus {n} --steps 20 --warmup 5 --no-cpu")
 
 
 # name -> [(step, timeout s, command, output extension)]
@@ -35,11 +35,12 @@ RECIPES = {
     "suite": [("gpu_suite", 900, PYTEST.format(t=240) + " -m gpu tests", "log")],
     "smoke": [("smoke", 180, "python3 -c 'import __graft_entry__ as g; g.smoke()'", "log")],
     "driver": [(f"bench_driver_{i}", 240, DRIVER, "json") for i in (1, 2, 3)],
-    "bench": [("bench_H", 300, "python3 bench.py --no-host", "json"),
-              ("bench_C5_n1", 300, "python3 bench.py --workload C5 --no-cpu", "json")],
-    "configs": [(f"bench_{w}", 240, f"python3 bench.py --workload {w} --no-cpu --no-host", "json")
+    "bench": [("bench_H", 300, "python3 bench.py --full --no-host", "json"),
+              ("bench_C5_n1", 300, "python3 bench.py --full --workload C5 --no-cpu", "json")],
+    "configs": [(f"bench_{w}", 240, f"python3 bench.py --full --workload {w} --no-cpu --no-host", "json")
                 for w in ("C2", "C3", "C4", "H8200")],
-    "putget": [(f"{x}_H", 200, f"python3 bench.py --xfer {x} --steps 50 --warmup 5 --no-cpu --no-host", "json")
+    "putget": [(f"{x}_H", 200, f"python3 bench.py --full --xfer {x} --steps 50 --warmup 5 --no-cpu --no-host",
+                "json")
                for x in ("put", "get")],
     "evidence": [("evidence", 900, "bash tools/evidence.sh r06", "log")],
     "iov": [("iov_tests", 300, PYTEST.format(t=120) + " -m gpu tests/test_gpu_parity.py -k 'one_workgroup or partitions_large or accv "
