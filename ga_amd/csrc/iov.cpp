@@ -374,6 +374,16 @@ static void translate_range(const uint64_t *in, int64_t delta, uint64_t *u, long
     *seq_out = off == 0;
 }
 
+// The progression test alone, for a list that is not translated (pageable host
+// destinations): does in[0..n) continue a0 + i * step from global index i0?
+__attribute__((optimize("O3"), target_clones("avx512f", "avx2", "default")))
+static uint64_t host_seq_range(const uint64_t *in, long n, uint64_t a0, long i0, uint64_t step) {
+    uint64_t off = 0;
+    const uint64_t e0 = a0 + (uint64_t)i0 * step;
+    for (long i = 0; i < n; ++i) off |= in[i] ^ (e0 + (uint64_t)i * step);
+    return off == 0;
+}
+
 // io-vector pairs from this many up have repeated destinations ordered on the GPU (the
 // hashed path, or launch_iov_runs) instead of a host-side overlap check (a sort of the
 // pairs): whole calls of 4095 pairs took 0.107 ms through the host check against 0.031
@@ -642,7 +652,23 @@ static bool iov_local(int cop, const void *scale, const uint64_t *src, const uin
         phase("kernels");
         GA_HIP(hipMemcpy(up + o_down, dev + o_res, (size_t)n * (size_t)bytes, hipMemcpyDeviceToHost));
         phase("results down");
-        par_for(n, par_threads(n), [&](int, long i0, long i1) {
+        // The ranges of a parallel scatter are written in no fixed order, so the pool is
+        // used only when no destination can be named from two ranges: the destinations
+        // one contiguous vector in pair order (GA's `v` of a gather; the progression test
+        // translate_range makes for device lists).  Any other list may repeat a
+        // destination, whose last pair must win (comex.c:7327-7400): one thread, pair order.
+        int T = par_threads(n);
+        if (T > 1) {
+            uint64_t sq[8];
+            const uint64_t a0 = (uint64_t)(uintptr_t)host_dst[0];
+            par_for(n, T, [&](int t, long i0, long i1) {
+                sq[t] = host_seq_range((const uint64_t *)host_dst + i0, i1 - i0, a0, i0, (uint64_t)bytes);
+            });
+            bool seq = true;
+            for (int t = 0; t < T; ++t) seq = seq && sq[t];
+            if (!seq) T = 1;
+        }
+        par_for(n, T, [&](int, long i0, long i1) {
             scatter_runs(host_dst + i0, up + o_down + i0 * (long)bytes, (int)(i1 - i0), bytes);
         });
         phase("host scatter");
@@ -827,7 +853,9 @@ int xfer_vec(Xfer kind, int op, void *scale, comex_giov_t *darr, int len, int pr
         if (!host_bounce && (src_host || dst_host) && !remote_apply) {
             // pageable host runs on one side (GA's MA buffer `v` of a scatter/gather): the
             // sources are gathered on the host and uploaded packed, or the results come
-            // back packed and are scattered on the host, in pair order
+            // back packed and are scattered on the host: on the pool when the destinations
+            // are one contiguous vector in pair order (none can repeat), else by one thread
+            // in pair order, so that a repeated destination keeps its last pair's bytes
             if (world != r.rank) fence_target(world);
             if (src_host) {   // gathered straight into the pinned upload staging
                 iov_local(cop, scale, nullptr, dv, bytes, n, nullptr, nullptr, 0, 0, darr[k].src);

@@ -1,7 +1,41 @@
-"""Comparison helpers shared by the parity tests."""
+"""Comparison helpers and case builders shared by the parity and fuzz tests."""
+import ctypes
+
 import numpy as np
 
 import cases as C
+
+
+def random_alpha(rng, op):
+    if op in (C.INT, C.LNG):
+        return int(rng.integers(-5, 6))
+    if op in (C.FLT, C.DBL):
+        return float(rng.uniform(-2, 2))
+    return complex(rng.uniform(-2, 2), rng.uniform(-2, 2))
+
+
+def phased_fill(op, nbytes, off, seed):
+    """fill values laid out from byte `off % esz` on, so that the elements a side
+    reads at an offset below the natural alignment are the generator's values, not
+    bit patterns straddling two of them (which include NaNs: the sign and payload of
+    a NaN that arithmetic produces are not pinned, so they would differ in the bytes)"""
+    ph = off % C.ESZ[op]
+    out = np.zeros(nbytes, dtype=np.uint8)
+    out[ph:] = C.fill_bytes(op, nbytes - ph, seed)
+    return out
+
+
+def _giov(src_addrs, dst_addrs, nbytes):
+    """one comex_giov_t over numpy uint64 address arrays (kept alive by the descriptor)"""
+    import ga_amd
+    src_addrs = np.ascontiguousarray(src_addrs, dtype=np.uint64)
+    dst_addrs = np.ascontiguousarray(dst_addrs, dtype=np.uint64)
+    g = ga_amd.GIOV()
+    g._keep = (src_addrs, dst_addrs)
+    g.src = ctypes.cast(ctypes.c_void_p(src_addrs.ctypes.data), ctypes.POINTER(ctypes.c_void_p))
+    g.dst = ctypes.cast(ctypes.c_void_p(dst_addrs.ctypes.data), ctypes.POINTER(ctypes.c_void_p))
+    g.count, g.bytes = len(src_addrs), nbytes
+    return g
 
 
 def same_bits_nan_aware(a, b, op):

@@ -26,21 +26,13 @@ import pytest
 
 import cases as C
 import ga_amd
-from helpers import first_mismatch, same_bits_nan_aware
+from helpers import _giov, first_mismatch, phased_fill, random_alpha, same_bits_nan_aware
 
 pytestmark = pytest.mark.gpu
 
 OPS = (C.INT, C.DBL, C.FLT, C.CPL, C.DCP, C.LNG)
 # GAAMD_FUZZ_SEED shifts every seed (soak runs: tools/sessions/r05_soak.sh); 0 is the suite's
 SEED = int(os.environ.get("GAAMD_FUZZ_SEED", "0")) * 100003
-
-
-def random_alpha(rng, op):
-    if op in (C.INT, C.LNG):
-        return int(rng.integers(-5, 6))
-    if op in (C.FLT, C.DBL):
-        return float(rng.uniform(-2, 2))
-    return complex(rng.uniform(-2, 2), rng.uniform(-2, 2))
 
 
 def random_side(rng, count, levels, esz, allow_overlap):
@@ -79,17 +71,6 @@ def random_case(rng, op):
         so += (do - so) % esz
     return dict(op=op, count=count, levels=levels, ss=ss, ds=ds, so=so, do=do, alias=alias,
                 alpha=random_alpha(rng, op))
-
-
-def phased_fill(op, nbytes, off, seed):
-    """fill values laid out from byte `off % esz` on, so that the elements a side
-    reads at an offset below the natural alignment are the generator's values, not
-    bit patterns straddling two of them (which include NaNs: the sign and payload of
-    a NaN that arithmetic produces are not pinned, so they would differ in the bytes)"""
-    ph = off % C.ESZ[op]
-    out = np.zeros(nbytes, dtype=np.uint8)
-    out[ph:] = C.fill_bytes(op, nbytes - ph, seed)
-    return out
 
 
 def run_case(L, oracle, k, case):
@@ -227,17 +208,6 @@ def test_random_pack_unpack_acc_and_puts(gpu_lib, oracle, seed):
         finally:
             sb.free()
             db.free()
-
-
-def _giov(src_addrs, dst_addrs, nbytes):
-    src_addrs = np.ascontiguousarray(src_addrs, dtype=np.uint64)
-    dst_addrs = np.ascontiguousarray(dst_addrs, dtype=np.uint64)
-    g = ga_amd.GIOV()
-    g._keep = (src_addrs, dst_addrs)
-    g.src = ctypes.cast(ctypes.c_void_p(src_addrs.ctypes.data), ctypes.POINTER(ctypes.c_void_p))
-    g.dst = ctypes.cast(ctypes.c_void_p(dst_addrs.ctypes.data), ctypes.POINTER(ctypes.c_void_p))
-    g.count, g.bytes = len(src_addrs), nbytes
-    return g
 
 
 def random_pairs(rng, n, nbytes, esz):
