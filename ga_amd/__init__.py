@@ -147,6 +147,51 @@ def unpack_acc(op, scale, packed, dst, dst_stride, count, stride_levels, stream=
         raise RuntimeError(f"gaamd_unpack_acc failed with {rc}")
 
 
+def ll_array(vals):
+    vals = list(vals) if vals is not None else []
+    return (ctypes.c_longlong * max(1, len(vals)))(*vals)
+
+
+# computing on a patch where it lies (gaamd_patch_*): count in elements per dimension
+# (dimension 0 contiguous), strides in bytes of dimensions 1..; the return code is
+# handed back (0, or the negative codes of ga_amd.h)
+def patch_fill(op, value, dst, dst_stride, count, stream=None):
+    keep, vp = scale_buffer(op, value)
+    return lib().gaamd_patch_fill(op, vp, ctypes.c_void_p(dst), ll_array(dst_stride), ll_array(count), len(count),
+                                  stream)
+
+
+def patch_scale(op, alpha, dst, dst_stride, count, stream=None):
+    keep, ap = scale_buffer(op, alpha)
+    return lib().gaamd_patch_scale(op, ap, ctypes.c_void_p(dst), ll_array(dst_stride), ll_array(count), len(count),
+                                   stream)
+
+
+def patch_add(op, alpha, a, a_stride, beta, b, b_stride, c, c_stride, count, stream=None):
+    ka, ap = scale_buffer(op, alpha)
+    kb, bp = scale_buffer(op, beta)
+    return lib().gaamd_patch_add(op, ap, ctypes.c_void_p(a), ll_array(a_stride), bp, ctypes.c_void_p(b),
+                                 ll_array(b_stride), ctypes.c_void_p(c), ll_array(c_stride), ll_array(count),
+                                 len(count), stream)
+
+
+def patch_dot(op, a, a_stride, b, b_stride, count, stream=None):
+    """(return code, one-element numpy array of the op's type)"""
+    out = np.zeros(1, dtype=OP_DTYPE[op])
+    rc = lib().gaamd_patch_dot(op, ctypes.c_void_p(a), ll_array(a_stride), ctypes.c_void_p(b), ll_array(b_stride),
+                               ll_array(count), len(count), out.ctypes.data_as(ctypes.c_void_p), stream)
+    return rc, out
+
+
+def patch_add_plan(op, a, a_stride, b, b_stride, c, c_stride, count):
+    """gaamd_patch_add's checks without a launch (no GPU): (code, {width, levels, rows, nvec})"""
+    out = (ctypes.c_longlong * 4)()
+    rc = lib().gaamd_patch_add_plan(op, ctypes.c_void_p(a), ll_array(a_stride), ctypes.c_void_p(b),
+                                    ll_array(b_stride), ctypes.c_void_p(c), ll_array(c_stride), ll_array(count),
+                                    len(count), out)
+    return rc, {"width": out[0], "levels": out[1], "rows": out[2], "nvec": out[3]}
+
+
 def last_launch():
     k, w, u, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     b = ctypes.c_ulonglong()

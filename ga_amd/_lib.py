@@ -15,6 +15,7 @@ GA_LIB_PATH = os.path.join(_HERE, "libga_amd_ga.so")
 DIAG_LIB_PATH = os.path.join(_HERE, "libga_amd_diag.so")
 
 c_int_p = ctypes.POINTER(ctypes.c_int)
+c_ll_p = ctypes.POINTER(ctypes.c_longlong)
 
 
 class DoubleComplex(ctypes.Structure):   # include/ga.h (comex/src-common/acc.h:6-10)
@@ -261,6 +262,17 @@ SIGNATURES = {
     "gaamd_wire_selftest": (ctypes.c_int, [ctypes.c_int]),
     "gaamd_strided": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, c_int_p, ctypes.c_void_p,
                                      c_int_p, c_int_p, ctypes.c_int, ctypes.c_void_p]),
+    "gaamd_patch_fill": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, c_ll_p, ctypes.c_int,
+                                        ctypes.c_void_p]),
+    "gaamd_patch_scale": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, c_ll_p,
+                                         ctypes.c_int, ctypes.c_void_p]),
+    "gaamd_patch_add": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, c_ll_p, ctypes.c_void_p, c_ll_p, c_ll_p, ctypes.c_int,
+                                       ctypes.c_void_p]),
+    "gaamd_patch_dot": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, c_ll_p, ctypes.c_void_p, c_ll_p, c_ll_p,
+                                       ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "gaamd_patch_add_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, c_ll_p, ctypes.c_void_p, c_ll_p,
+                                            ctypes.c_void_p, c_ll_p, c_ll_p, ctypes.c_int, c_ll_p]),
     "gaamd_packed_size": (ctypes.c_long, [c_int_p, ctypes.c_int]),
     "gaamd_pack": (ctypes.c_int, [ctypes.c_void_p, c_int_p, c_int_p, ctypes.c_int, ctypes.c_void_p,
                                   ctypes.c_void_p]),
@@ -323,6 +335,8 @@ SIGNATURES = {
 }
 
 # ga.h: libga_amd_ga.so
+_DOT_TYPES = {"I": ctypes.c_int, "L": ctypes.c_long, "F": ctypes.c_float, "D": ctypes.c_double,
+              "C": SingleComplex, "Z": DoubleComplex}
 GA_SIGNATURES = {
     "gaamd_ga_proc_grid": (ctypes.c_int, [ctypes.c_int, c_int_p, c_int_p, ctypes.c_int, c_int_p]),
     "GA_Initialize": (ctypes.c_int, []),
@@ -359,6 +373,24 @@ GA_SIGNATURES = {
     "NGA_Release_update": (None, [ctypes.c_int, c_int_p, c_int_p]),
     "GA_Get_proc_grid": (None, [ctypes.c_int, c_int_p]),
     "GA_Print_stats": (None, []),
+    # computing on arrays where they lie
+    "GA_Duplicate": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p]),
+    "GA_Compare_distr": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "NGA_Inquire": (None, [ctypes.c_int, c_int_p, c_int_p, c_int_p]),
+    "GA_Fill": (None, [ctypes.c_int, ctypes.c_void_p]),
+    "GA_Scale": (None, [ctypes.c_int, ctypes.c_void_p]),
+    "GA_Add": (None, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    "GA_Copy": (None, [ctypes.c_int, ctypes.c_int]),
+    "NGA_Fill_patch": (None, [ctypes.c_int, c_int_p, c_int_p, ctypes.c_void_p]),
+    "NGA_Zero_patch": (None, [ctypes.c_int, c_int_p, c_int_p]),
+    "NGA_Scale_patch": (None, [ctypes.c_int, c_int_p, c_int_p, ctypes.c_void_p]),
+    "NGA_Add_patch": (None, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_int_p, ctypes.c_void_p, ctypes.c_int,
+                             c_int_p, c_int_p, ctypes.c_int, c_int_p, c_int_p]),
+    "NGA_Copy_patch": (None, [ctypes.c_char, ctypes.c_int, c_int_p, c_int_p, ctypes.c_int, c_int_p, c_int_p]),
+    **{f"GA_{n}dot": (t, [ctypes.c_int, ctypes.c_int]) for n, t in _DOT_TYPES.items()},
+    **{f"NGA_{n}dot_patch": (t, [ctypes.c_int, ctypes.c_char, c_int_p, c_int_p, ctypes.c_int, ctypes.c_char,
+                                 c_int_p, c_int_p]) for n, t in _DOT_TYPES.items()},
+    "gaamd_ga_live_arrays": (ctypes.c_int, []),
 }
 SIGNATURES.update(GA_SIGNATURES)
 

@@ -807,6 +807,7 @@ int comex_finalize() {
     if (g_get_scratch_ev) (void)hipEventDestroy(g_get_scratch_ev);
     g_get_scratch_ev = nullptr;
     iov_finalize();
+    patch_release();                    // every thread's dot-product scratch
     views_finalize();
     (void)hipStreamDestroy(r.stream);
     r.stream = nullptr;

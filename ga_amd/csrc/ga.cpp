@@ -26,6 +26,7 @@
 #pragma GCC visibility push(default)
 #include "../../include/ga.h"
 #include "../../include/armci.h"
+#include "../../include/message.h"
 #include "../../include/comex.h"
 #include "../../include/ga_amd.h"
 #pragma GCC visibility pop
@@ -82,6 +83,9 @@ static std::vector<GArray> g_arrays;
 static struct {
     long numacc = 0, numput = 0, numget = 0, numsca = 0, numgat = 0;
     double acctot = 0, accloc = 0, scatot = 0, scaloc = 0, gattot = 0, gatloc = 0;
+    // calls that compute on the arrays where they lie, and the bytes this rank's kernels moved
+    long numfill = 0, numscale = 0, numadd = 0, numcopy = 0, numdot = 0;
+    double mathloc = 0;
 } g_stat;
 
 static GArray &arr(int g_a) {
@@ -875,7 +879,410 @@ int gaamd_ga_proc_grid(int ndim, const int *dims, const int *chunk, int npes, in
     return 0;
 }
 
+// ---- computing on arrays where they lie ------------------------------------------
+// GA_Fill / GA_Scale / GA_Add / GA_Copy / GA_?dot and their patch forms
+// (global/src/global.npatch.c, global.nalg.c; capi.c names and argument orders).
+// Every block is in HBM, so each rank runs one gfx950 kernel on its own part of the
+// patch (ga_amd.h gaamd_patch_*) where the reference runs a host loop.  All are
+// collective with the reference's sync discipline: GA_Sync on entry, the local work
+// on gaamd_stream(), a stream sync, GA_Sync on exit; the dot products end in the sum
+// over ranks (armci_msg_?gop "+", as pnga_gop) instead of the exit sync.
+//   fast path ("compatible", npatch.c:2698-2737, 1207-1247): equal block maps and
+//     equal patches -- every rank's operands share its block's leading dimensions;
+//   general path: the odd operand is copied into a GA_Duplicate of the output (of
+//     g_a for dot) with NGA_Copy_patch first, as the reference does.
+// Transposes, reshapes and arrays in a host segment abort: nothing here computes on
+// the host.
+
+// this rank's part of the patch [lo, hi] (Fortran order, 1-based): its address in
+// the block, the counts and the byte strides the block's extents give
+struct Sub {
+    bool any = false;
+    char *p = nullptr;
+    long plo[GA_MAX_DIM], phi[GA_MAX_DIM], ext[GA_MAX_DIM];
+    long long count[GA_MAX_DIM], stride[GA_MAX_DIM];
+    double bytes = 0;
+};
+
+static Sub own_sub(const GArray &a, const long *lo, const long *hi) {
+    Sub s;
+    long blo[GA_MAX_DIM], bhi[GA_MAX_DIM];
+    if (block_elems(a, my_rank(), blo, bhi) == 0) return s;
+    for (int d = 0; d < a.ndim; d++) {
+        s.plo[d] = std::max(lo[d], blo[d]);
+        s.phi[d] = std::min(hi[d], bhi[d]);
+        if (s.plo[d] > s.phi[d]) return s;
+    }
+    long long off = 0, f = 1;
+    s.bytes = a.elemsize;
+    for (int d = 0; d < a.ndim; d++) {
+        s.ext[d] = bhi[d] - blo[d] + 1;
+        off += (s.plo[d] - blo[d]) * f;
+        f *= s.ext[d];
+        s.count[d] = s.phi[d] - s.plo[d] + 1;
+        s.stride[d] = f * a.elemsize;   // byte stride of dimension d + 1
+        s.bytes *= (double)s.count[d];
+    }
+    s.p = (char *)a.ptr[my_rank()] + off * a.elemsize;
+    s.any = true;
+    return s;
+}
+
+static void need_hbm(const GArray &a, const char *what) {
+    void *p = a.ptr[my_rank()];
+    if (p && gaamd_segment_kind(p) == 2)
+        fatal("%s: array '%s' lives in a host segment (COMEX_AMD_SEGMENT=host); "
+              "computing on host-segment arrays is not supported", what, a.name.c_str());
+}
+
+static void check_patch(const GArray &a, const long *lo, const long *hi, const char *what) {
+    for (int d = 0; d < a.ndim; d++)
+        if (lo[d] < 1 || hi[d] > a.dims[d] || lo[d] > hi[d]) fatal("%s: patch out of range in dim %d", what, d);
+}
+
+// pnga_compare_distr (base.c): equal shapes and equal block maps
+static bool same_distr(const GArray &a, const GArray &b) {
+    if (a.ndim != b.ndim) return false;
+    for (int d = 0; d < a.ndim; d++)
+        if (a.dims[d] != b.dims[d] || a.nblock[d] != b.nblock[d] || a.map[d] != b.map[d]) return false;
+    return true;
+}
+
+static bool same_patch(int nd, const long *alo, const long *ahi, const long *blo, const long *bhi) {
+    for (int d = 0; d < nd; d++)
+        if (alo[d] != blo[d] || ahi[d] != bhi[d]) return false;
+    return true;
+}
+
+// patches of equal rank and extents (anything else is a reshape)
+static void need_same_shape(const GArray &a, const long *alo, const long *ahi, const GArray &b, const long *blo,
+                            const long *bhi, const char *what) {
+    bool same = a.ndim == b.ndim;
+    for (int d = 0; same && d < a.ndim; d++) same = ahi[d] - alo[d] == bhi[d] - blo[d];
+    if (!same)
+        fatal("%s: patches of different rank or extents (a reshape) are not supported", what);
+}
+
+static void need_no_trans(char t, const char *what) {
+    if (t != 'n' && t != 'N') fatal("%s: transposed patches (trans '%c') are not supported", what, t);
+}
+
+static void math_end(const char *what) {
+    if (gaamd_sync(gaamd_stream()) != 0) fatal("%s: the stream failed", what);
+    comex_barrier(COMEX_GROUP_WORLD);
+}
+
+static void whole(const GArray &a, long *lo, long *hi) {
+    for (int d = 0; d < a.ndim; d++) { lo[d] = 1; hi[d] = a.dims[d]; }
+}
+
+int GA_Duplicate(int g_a, char *array_name) {
+    GArray n = arr(g_a);   // type, shape and block map (pnga_duplicate, base.c)
+    n.name = array_name ? array_name : "";
+    n.live = false;
+    n.ptr.clear();
+    return allocate(n);
+}
+
+int GA_Compare_distr(int g_a, int g_b) { return same_distr(arr(g_a), arr(g_b)) ? 0 : 1; }   // capi.c:2375: 0 = same
+
+void NGA_Inquire(int g_a, int *type, int *ndim, int dims[]) {
+    GArray &a = arr(g_a);
+    *type = a.type;
+    *ndim = a.ndim;
+    for (int i = 0; i < a.ndim; i++) dims[a.ndim - 1 - i] = (int)a.dims[i];
+}
+
+int gaamd_ga_live_arrays(void) {
+    int n = 0;
+    for (const GArray &a : g_arrays) n += a.live ? 1 : 0;
+    return n;
+}
+
+enum MapKind { M_FILL, M_SCALE };
+static void map_patch(MapKind kind, int g_a, const long *lo, const long *hi, const void *val, const char *what) {
+    GArray &a = arr(g_a);
+    need_hbm(a, what);
+    check_patch(a, lo, hi, what);
+    comex_barrier(COMEX_GROUP_WORLD);   // fences every pending one-sided operation, then syncs
+    const Sub s = own_sub(a, lo, hi);
+    (kind == M_FILL ? g_stat.numfill : g_stat.numscale)++;
+    if (s.any) {
+        const int rc = kind == M_FILL
+                           ? gaamd_patch_fill(a.optype, val, s.p, s.stride, s.count, a.ndim, gaamd_stream())
+                           : gaamd_patch_scale(a.optype, val, s.p, s.stride, s.count, a.ndim, gaamd_stream());
+        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        g_stat.mathloc += s.bytes * (kind == M_FILL ? 1 : 2);
+    }
+    math_end(what);
+}
+
+// a block-local copy of any size through gaamd_strided's int geometry: contiguous
+// dimensions merged, a 1-D run in pieces of 1 GiB
+static void local_copy(const Sub &s, const Sub &t, int nd, int esz, const char *what) {
+    long long cnt[GA_MAX_DIM] = {0}, ss[GA_MAX_DIM] = {0}, ds[GA_MAX_DIM] = {0};
+    int n = nd;
+    for (int d = 0; d < nd; d++) { cnt[d] = s.count[d]; ss[d] = s.stride[d]; ds[d] = t.stride[d]; }
+    cnt[0] *= esz;   // bytes
+    while (n > 1 && ss[0] == cnt[0] && ds[0] == cnt[0]) {
+        cnt[0] *= cnt[1];
+        for (int d = 1; d + 1 < n; d++) { cnt[d] = cnt[d + 1]; ss[d - 1] = ss[d]; ds[d - 1] = ds[d]; }
+        --n;
+    }
+    const long long piece = 1ll << 30;
+    if (n == 1) {
+        for (long long o = 0; o < cnt[0]; o += piece) {
+            int c = (int)std::min(piece, cnt[0] - o);
+            if (gaamd_strided(GAAMD_OP_COPY, nullptr, s.p + o, nullptr, t.p + o, nullptr, &c, 0, gaamd_stream()))
+                fatal("%s: copy kernel failed", what);
+        }
+        return;
+    }
+    int ic[GA_MAX_DIM], is[GA_MAX_DIM], id[GA_MAX_DIM];
+    for (int d = 0; d < n; d++) {
+        if (cnt[d] >= (1ll << 31) || (d < n - 1 && (ss[d] >= (1ll << 31) || ds[d] >= (1ll << 31))))
+            fatal("%s: a strided block-local copy past 2 GiB is not supported", what);
+        ic[d] = (int)cnt[d];
+        is[d] = (int)ss[d];
+        id[d] = (int)ds[d];
+    }
+    if (gaamd_strided(GAAMD_OP_COPY, nullptr, s.p, is, t.p, id, ic, n - 1, gaamd_stream()))
+        fatal("%s: copy kernel failed", what);
+}
+
+// pnga_copy_patch (global.npatch.c:560-935), trans 'N', equal rank and extents: each
+// rank cuts the source patch by its own block and puts that part, from HBM, into g_b
+// at the shifted position; where both blocks coincide it is one local copy kernel
+static void copy_patch(int g_a, const long *alo, const long *ahi, int g_b, const long *blo, const long *bhi,
+                       const char *what) {
+    GArray &a = arr(g_a), &b = arr(g_b);
+    if (a.type != b.type) fatal("%s: types of '%s' and '%s' differ", what, a.name.c_str(), b.name.c_str());
+    need_hbm(a, what);
+    need_hbm(b, what);
+    if (a.ndim != b.ndim) fatal("%s: arrays of different rank (a reshape) are not supported", what);
+    check_patch(a, alo, ahi, what);
+    check_patch(b, blo, bhi, what);
+    need_same_shape(a, alo, ahi, b, blo, bhi, what);
+    const int nd = a.ndim;
+    if (g_a == g_b && !same_patch(nd, alo, ahi, blo, bhi)) {
+        bool meet = true;
+        for (int d = 0; d < nd; d++) meet = meet && alo[d] <= bhi[d] && blo[d] <= ahi[d];
+        if (meet) fatal("%s: overlapping patches of one array", what);   // npatch.c: "arrays overlap"
+    }
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_stat.numcopy++;
+    const Sub s = own_sub(a, alo, ahi);
+    if (s.any && !(g_a == g_b && same_patch(nd, alo, ahi, blo, bhi))) {
+        long dlo[GA_MAX_DIM], dhi[GA_MAX_DIM], ld[GA_MAX_DIM];
+        bool here = same_distr(a, b);
+        for (int d = 0; d < nd; d++) {
+            dlo[d] = blo[d] + (s.plo[d] - alo[d]);
+            dhi[d] = dlo[d] + (s.phi[d] - s.plo[d]);
+            ld[d] = s.ext[d];
+            here = here && dlo[d] == s.plo[d];
+        }
+        if (here) {
+            const Sub t = own_sub(b, dlo, dhi);
+            local_copy(s, t, nd, a.elemsize, what);
+        } else {
+            patch_op(GA_PUT, g_b, dlo, dhi, s.p, ld, nullptr);
+        }
+        g_stat.mathloc += 2 * s.bytes;
+    }
+    math_end(what);
+}
+
+static void add_patch(void *alpha, int g_a, const long *alo, const long *ahi, void *beta, int g_b, const long *blo,
+                      const long *bhi, int g_c, const long *clo, const long *chi, const char *what) {
+    int tmp[2] = {0, 0}, use[2] = {g_a, g_b};
+    {
+        GArray &a = arr(g_a), &b = arr(g_b), &c = arr(g_c);
+        if (a.type != c.type || b.type != c.type) fatal("%s: types of the arrays differ", what);
+        need_hbm(a, what);
+        need_hbm(b, what);
+        need_hbm(c, what);
+        check_patch(a, alo, ahi, what);
+        check_patch(b, blo, bhi, what);
+        check_patch(c, clo, chi, what);
+        need_same_shape(a, alo, ahi, c, clo, chi, what);
+        need_same_shape(b, blo, bhi, c, clo, chi, what);
+    }
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_stat.numadd++;
+    const long *lo[2] = {alo, blo}, *hi[2] = {ahi, bhi};
+    for (int k = 0; k < 2; k++) {
+        const bool ok = same_distr(arr(use[k]), arr(g_c)) && same_patch(arr(g_c).ndim, lo[k], hi[k], clo, chi);
+        if (ok) continue;
+        char name[] = "ga_amd add temporary";
+        tmp[k] = GA_Duplicate(g_c, name);
+        copy_patch(use[k], lo[k], hi[k], tmp[k], clo, chi, what);
+        use[k] = tmp[k];
+    }
+    GArray &c = arr(g_c);
+    const Sub sc = own_sub(c, clo, chi);
+    if (sc.any) {
+        const Sub sa = own_sub(arr(use[0]), clo, chi), sb = own_sub(arr(use[1]), clo, chi);
+        const int rc = gaamd_patch_add(c.optype, alpha, sa.p, sa.stride, beta, sb.p, sb.stride, sc.p, sc.stride,
+                                       sc.count, c.ndim, gaamd_stream());
+        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        g_stat.mathloc += 3 * sc.bytes;
+    }
+    math_end(what);
+    for (int k = 0; k < 2; k++)
+        if (tmp[k]) destroy(tmp[k]);
+}
+
+// every rank returns the same bits: the local sums are combined by armci_msg_?gop
+static void dot_patch(int type, int g_a, char t_a, const long *alo, const long *ahi, int g_b, char t_b,
+                      const long *blo, const long *bhi, void *result, const char *what) {
+    int tmp = 0, use_b = g_b;
+    {
+        GArray &a = arr(g_a), &b = arr(g_b);
+        if (a.type != type || b.type != type)
+            fatal("%s: type mismatch: arrays of type %d and %d in a call for type %d", what, a.type, b.type, type);
+        need_no_trans(t_a, what);
+        need_no_trans(t_b, what);
+        need_hbm(a, what);
+        need_hbm(b, what);
+        check_patch(a, alo, ahi, what);
+        check_patch(b, blo, bhi, what);
+        need_same_shape(a, alo, ahi, b, blo, bhi, what);
+    }
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_stat.numdot++;
+    if (!(same_distr(arr(g_a), arr(g_b)) && same_patch(arr(g_a).ndim, alo, ahi, blo, bhi))) {
+        char name[] = "ga_amd dot temporary";
+        tmp = GA_Duplicate(g_a, name);
+        copy_patch(g_b, blo, bhi, tmp, alo, ahi, what);
+        use_b = tmp;
+    }
+    GArray &a = arr(g_a);
+    double res[2] = {0.0, 0.0};   // 16 zero bytes: the zero of every type
+    const Sub sa = own_sub(a, alo, ahi);
+    if (sa.any) {
+        const Sub sb = own_sub(arr(use_b), alo, ahi);
+        const int rc = gaamd_patch_dot(a.optype, sa.p, sa.stride, sb.p, sb.stride, sa.count, a.ndim, res,
+                                       gaamd_stream());
+        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        g_stat.mathloc += 2 * sa.bytes;
+    }
+    char plus[] = "+";
+    switch (type) {
+    case C_INT: armci_msg_igop((int *)res, 1, plus); break;
+    case C_LONG: armci_msg_lgop((long *)res, 1, plus); break;
+    case C_FLOAT: armci_msg_fgop((float *)res, 1, plus); break;
+    case C_DBL: armci_msg_dgop(res, 1, plus); break;
+    case C_SCPL: armci_msg_fgop((float *)res, 2, plus); break;
+    case C_DCPL: armci_msg_dgop(res, 2, plus); break;
+    }
+    memcpy(result, res, (size_t)a.elemsize);
+    if (tmp) destroy(tmp);
+}
+
+void NGA_Fill_patch(int g_a, int lo[], int hi[], void *val) {
+    long flo[GA_MAX_DIM], fhi[GA_MAX_DIM];
+    c2f_index(arr(g_a).ndim, lo, flo);
+    c2f_index(arr(g_a).ndim, hi, fhi);
+    map_patch(M_FILL, g_a, flo, fhi, val, "NGA_Fill_patch");
+}
+void NGA_Zero_patch(int g_a, int lo[], int hi[]) {
+    long flo[GA_MAX_DIM], fhi[GA_MAX_DIM];
+    const double zero[2] = {0.0, 0.0};
+    c2f_index(arr(g_a).ndim, lo, flo);
+    c2f_index(arr(g_a).ndim, hi, fhi);
+    map_patch(M_FILL, g_a, flo, fhi, zero, "NGA_Zero_patch");
+}
+void NGA_Scale_patch(int g_a, int lo[], int hi[], void *alpha) {
+    long flo[GA_MAX_DIM], fhi[GA_MAX_DIM];
+    c2f_index(arr(g_a).ndim, lo, flo);
+    c2f_index(arr(g_a).ndim, hi, fhi);
+    map_patch(M_SCALE, g_a, flo, fhi, alpha, "NGA_Scale_patch");
+}
+void GA_Fill(int g_a, void *value) {
+    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
+    whole(arr(g_a), lo, hi);
+    map_patch(M_FILL, g_a, lo, hi, value, "GA_Fill");
+}
+void GA_Scale(int g_a, void *value) {
+    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
+    whole(arr(g_a), lo, hi);
+    map_patch(M_SCALE, g_a, lo, hi, value, "GA_Scale");
+}
+
+void NGA_Copy_patch(char trans, int g_a, int alo[], int ahi[], int g_b, int blo[], int bhi[]) {
+    need_no_trans(trans, "NGA_Copy_patch");
+    long fal[GA_MAX_DIM], fah[GA_MAX_DIM], fbl[GA_MAX_DIM], fbh[GA_MAX_DIM];
+    c2f_index(arr(g_a).ndim, alo, fal);
+    c2f_index(arr(g_a).ndim, ahi, fah);
+    c2f_index(arr(g_b).ndim, blo, fbl);
+    c2f_index(arr(g_b).ndim, bhi, fbh);
+    copy_patch(g_a, fal, fah, g_b, fbl, fbh, "NGA_Copy_patch");
+}
+void GA_Copy(int g_a, int g_b) {
+    long al[GA_MAX_DIM], ah[GA_MAX_DIM], bl[GA_MAX_DIM], bh[GA_MAX_DIM];
+    whole(arr(g_a), al, ah);
+    whole(arr(g_b), bl, bh);
+    copy_patch(g_a, al, ah, g_b, bl, bh, "GA_Copy");
+}
+
+void NGA_Add_patch(void *alpha, int g_a, int alo[], int ahi[], void *beta, int g_b, int blo[], int bhi[], int g_c,
+                   int clo[], int chi[]) {
+    long l[3][GA_MAX_DIM], h[3][GA_MAX_DIM];
+    c2f_index(arr(g_a).ndim, alo, l[0]);
+    c2f_index(arr(g_a).ndim, ahi, h[0]);
+    c2f_index(arr(g_b).ndim, blo, l[1]);
+    c2f_index(arr(g_b).ndim, bhi, h[1]);
+    c2f_index(arr(g_c).ndim, clo, l[2]);
+    c2f_index(arr(g_c).ndim, chi, h[2]);
+    add_patch(alpha, g_a, l[0], h[0], beta, g_b, l[1], h[1], g_c, l[2], h[2], "NGA_Add_patch");
+}
+void GA_Add(void *alpha, int g_a, void *beta, int g_b, int g_c) {
+    long l[3][GA_MAX_DIM], h[3][GA_MAX_DIM];
+    whole(arr(g_a), l[0], h[0]);
+    whole(arr(g_b), l[1], h[1]);
+    whole(arr(g_c), l[2], h[2]);
+    add_patch(alpha, g_a, l[0], h[0], beta, g_b, l[1], h[1], g_c, l[2], h[2], "GA_Add");
+}
+
+static void c_dot_patch(int type, int g_a, char t_a, int alo[], int ahi[], int g_b, char t_b, int blo[], int bhi[],
+                        void *res, const char *what) {
+    long fal[GA_MAX_DIM], fah[GA_MAX_DIM], fbl[GA_MAX_DIM], fbh[GA_MAX_DIM];
+    c2f_index(arr(g_a).ndim, alo, fal);
+    c2f_index(arr(g_a).ndim, ahi, fah);
+    c2f_index(arr(g_b).ndim, blo, fbl);
+    c2f_index(arr(g_b).ndim, bhi, fbh);
+    dot_patch(type, g_a, t_a, fal, fah, g_b, t_b, fbl, fbh, res, what);
+}
+static void c_dot(int type, int g_a, int g_b, void *res, const char *what) {
+    long al[GA_MAX_DIM], ah[GA_MAX_DIM], bl[GA_MAX_DIM], bh[GA_MAX_DIM];
+    whole(arr(g_a), al, ah);
+    whole(arr(g_b), bl, bh);
+    dot_patch(type, g_a, 'n', al, ah, g_b, 'n', bl, bh, res, what);
+}
+
+#define GAAMD_DOT(T, NAME, CODE)                                                                          \
+    T GA_##NAME(int g_a, int g_b) {                                                                        \
+        T v;                                                                                               \
+        c_dot(CODE, g_a, g_b, &v, "GA_" #NAME);                                                            \
+        return v;                                                                                          \
+    }                                                                                                      \
+    T NGA_##NAME##_patch(int g_a, char t_a, int alo[], int ahi[], int g_b, char t_b, int blo[], int bhi[]) { \
+        T v;                                                                                               \
+        c_dot_patch(CODE, g_a, t_a, alo, ahi, g_b, t_b, blo, bhi, &v, "NGA_" #NAME "_patch");              \
+        return v;                                                                                          \
+    }
+GAAMD_DOT(int, Idot, C_INT)
+GAAMD_DOT(long, Ldot, C_LONG)
+GAAMD_DOT(float, Fdot, C_FLOAT)
+GAAMD_DOT(double, Ddot, C_DBL)
+GAAMD_DOT(SingleComplex, Cdot, C_SCPL)
+GAAMD_DOT(DoubleComplex, Zdot, C_DCPL)
+#undef GAAMD_DOT
+
 void GA_Print_stats(void) {
+    printf("[%d] GA on-device calls: fill %ld, scale %ld, add %ld, copy %ld, dot %ld; local bytes moved %.0f\n",
+           my_rank(), g_stat.numfill, g_stat.numscale, g_stat.numadd, g_stat.numcopy, g_stat.numdot,
+           g_stat.mathloc);
     printf("[%d] GA statistics: acc calls %ld, put calls %ld, get calls %ld, scatter calls %ld, gather calls %ld\n",
            my_rank(), g_stat.numacc, g_stat.numput, g_stat.numget, g_stat.numsca, g_stat.numgat);
     printf("[%d] accumulate bytes total %.0f, local %.0f (%.1f%%)\n", my_rank(), g_stat.acctot, g_stat.accloc,

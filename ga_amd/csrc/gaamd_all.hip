@@ -7,3 +7,4 @@
 #include "gaamd_kernels.hip"
 #include "gaamd_iov.hip"
 #include "gaamd_misc.hip"
+#include "gaamd_patch.hip"

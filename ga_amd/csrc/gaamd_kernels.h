@@ -110,6 +110,37 @@ void side_span_host(const int *stride, const int *count, int stride_levels, int6
 
 int elem_size(int op);            // bytes per element for op; 1 for copy; 0 if unknown
 
+// ---- computing on a patch where it lies (gaamd_patch.hip) --------------------
+// op = COMEX_ACC_* names the element type; count[] in elements per dimension
+// (dimension 0 contiguous), stride[j] = byte stride of dimension j+1, ndim 1..7.
+// A count of zero is success without a launch.
+constexpr int kPatchMaxLevels = 6;     // row levels of a 7-dimensional patch
+constexpr int kPatchErrNdim = -2;      // ndim outside 1..7
+constexpr int kPatchErrCount = -3;     // a negative (or missing) count
+constexpr int kPatchErrOp = -4;        // not a COMEX_ACC_* type
+constexpr int kPatchErrScalar = -5;    // a missing value / alpha / beta / result
+constexpr int kPatchErrStride = -6;    // ndim > 1 without strides
+constexpr int kPatchErrRange = -7;     // 2^31 rows or more after merging
+constexpr int kPatchErrAlign = -8;     // a base or stride below 4-byte alignment
+constexpr int kPatchErrOverlap = -11;  // add: c overlaps an input without being exactly it
+int launch_patch_fill(int op, const void *value, void *dst, const long long *dst_stride, const long long *count,
+                      int ndim, hipStream_t stream);
+int launch_patch_scale(int op, const void *alpha, void *dst, const long long *dst_stride, const long long *count,
+                       int ndim, hipStream_t stream);
+int launch_patch_add(int op, const void *alpha, const void *a, const long long *a_stride, const void *beta,
+                     const void *b, const long long *b_stride, void *c, const long long *c_stride,
+                     const long long *count, int ndim, hipStream_t stream);
+// synchronises `stream` and writes one element to `result` (host)
+int launch_patch_dot(int op, const void *a, const long long *a_stride, const void *b, const long long *b_stride,
+                     const long long *count, int ndim, void *result, hipStream_t stream);
+struct PatchPlan;
+// launch_patch_add's checks without a launch (no device): 0 launch, 1 nothing to do, < 0 error;
+// plan[0..3] = {vector width, row levels after merging, rows, vectors per row}
+int plan_patch_add(int op, const void *a, const long long *a_stride, const void *b, const long long *b_stride,
+                   const void *c, const long long *c_stride, const long long *count, int ndim, long long plan[4],
+                   PatchPlan *out = nullptr);
+void patch_release();   // comex_finalize: every thread's dot-product scratch (streams idle)
+
 // comex_rmw: fetch-and-add (swap == 0) or swap of one 4- or 8-byte word at
 // `addr` (device-accessible); the old value lands in *out_dev (8 bytes)
 int launch_rmw(int swap, void *addr, int bytes, uint64_t val, uint64_t *out_dev, hipStream_t stream);

@@ -1,0 +1,774 @@
+// gaamd_patch.hip -- gfx950 kernels that compute on a patch of a global array
+// where it lies (HBM): fill, scale, add and the dot product, with their host
+// launchers (ga_amd.h section 2: gaamd_patch_fill/_scale/_add/_dot).
+//
+// Reference arithmetic (global/src/global.npatch.c), expression for expression:
+//   fill           stores the value                               1528-1650
+//   scale, real    x *= alpha                                     1953-1966
+//   scale, complex re = x.re*al.re - x.im*al.im
+//                  im = al.im*x.re + x.im*al.re                   1976-1986
+//   add, real      c = alpha*a + beta*b (two products, one sum)   2520-2525
+//   add, complex   c.re = x.re*a.re - x.im*a.im + y.re*b.re - y.im*b.im
+//                  c.im = x.re*a.im + x.im*a.re + y.re*b.im + y.im*b.re   2537-2546
+//   dot            sum += a*b; complex (no conjugate)
+//                  re += a.re*b.re - b.im*a.im; im += a.im*b.re + b.im*a.re   938-1095
+// Integers in unsigned arithmetic (two's-complement wraparound).  FP contraction is
+// off (pragma below and -ffp-contract=off): no FMA in any of these kernels.
+//
+// Geometry: count[] in elements per dimension (dimension 0 contiguous), byte strides
+// of dimensions 1.., all 64-bit.  The host drops count-1 dimensions and merges
+// contiguous ones (a whole block becomes one long row), then:
+//   * MAP kernel (fill, scale, add): grid = (chunks of a row) x (rows of this launch);
+//     a block streams BS*U W-byte vectors of one row, W = 16 where every base, stride
+//     and the row length allow, 8 or 4 otherwise; non-temporal loads and stores; the
+//     row decode is wave-uniform.  No loop and no division by the chunk count.
+//   * DOT kernel: work item = (row, chunk of kDotBS vectors); workgroup g sums the
+//     fixed range of items [g*kDotItems, (g+1)*kDotItems): each lane its own vectors
+//     in item order, the lanes of a wave by a shuffle tree, the waves through LDS in
+//     wave order; one partial per workgroup goes to device scratch.  A second launch
+//     of one workgroup adds the partials (lane t takes partials t*kFinalPer.. of every
+//     pass of kDotBS*kFinalPer, then the same tree) and stores the result into mapped
+//     pinned host memory.  Nothing depends on timing, the stream or the number of
+//     compute units: the same input gives the same bits.  No atomics.
+#pragma clang fp contract(off)
+
+#include "gaamd_kernels.h"
+#include "gaamd_device.hpp"
+#include <string.h>
+#include <mutex>
+#include <vector>
+
+namespace gaamd {
+
+struct PatchDesc {
+    char *p[3];                          // operand bases ([0]: the output; dot: a, b)
+    int64_t str[3][kPatchMaxLevels];     // byte stride of row level j, per operand
+    FastDiv cnt[kPatchMaxLevels];        // rows of level j
+    int32_t levels;
+    uint32_t row0;                       // first row of this launch
+    uint64_t nvec;                       // W-byte vectors per row
+};
+
+// byte offsets of row r for the first NP operands.  LV == 1: at most one row level
+// (2-D patches, contiguous runs): row r sits at r * stride, no digits.  LV == 0: mixed
+// radix over all kPatchMaxLevels levels, level 0 fastest, without a branch -- the host
+// fills the levels a patch does not have with count 1 and stride 0.
+template <int NP, int LV>
+__device__ __forceinline__ void patch_row(const PatchDesc &d, uint32_t r, int64_t (&off)[NP]) {
+    if constexpr (LV == 1) {
+#pragma unroll
+        for (int k = 0; k < NP; ++k) off[k] = (int64_t)r * d.str[k][0];
+    } else {
+#pragma unroll
+        for (int k = 0; k < NP; ++k) off[k] = 0;
+#pragma unroll
+        for (int j = 0; j < kPatchMaxLevels; ++j) {
+            const uint32_t q = d.cnt[j].div(r);
+            const uint32_t dig = r - q * d.cnt[j].d;
+#pragma unroll
+            for (int k = 0; k < NP; ++k) off[k] += (int64_t)dig * d.str[k][j];
+            r = q;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// element operations on one W-byte vector.  kOps: operand pointers; kIn: vectors
+// loaded (0: none; 1: the output itself; 2: operands 1 and 2)
+struct PatchFill {
+    static constexpr int kOps = 1, kIn = 0;
+    Scale16 pat;   // the value repeated over 16 bytes
+    template <int W>
+    __device__ __forceinline__ typename Vec<W>::T apply(typename Vec<W>::T, typename Vec<W>::T) const {
+        union { Scale16 s; typename Vec<W>::T v; } u;
+        u.s = pat;
+        return u.v;
+    }
+};
+
+template <typename A>
+struct PatchScaleReal {
+    static constexpr int kOps = 1, kIn = 1;
+    A s;
+    template <int W>
+    __device__ __forceinline__ typename Vec<W>::T apply(typename Vec<W>::T xv, typename Vec<W>::T) const {
+        constexpr int N = W / (int)sizeof(A);
+        union { typename Vec<W>::T v; A t[N]; } x;
+        x.v = xv;
+#pragma unroll
+        for (int i = 0; i < N; ++i) x.t[i] = x.t[i] * s;
+        return x.v;
+    }
+};
+
+template <typename R>
+struct PatchScaleCplx {
+    static constexpr int kOps = 1, kIn = 1;
+    R ar, ai;
+    template <int W>
+    __device__ __forceinline__ typename Vec<W>::T apply(typename Vec<W>::T xv, typename Vec<W>::T) const {
+        constexpr int N = W / (int)(2 * sizeof(R));
+        union { typename Vec<W>::T v; R t[2 * N]; } x;
+        x.v = xv;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const R xr = x.t[2 * i], xi = x.t[2 * i + 1];
+            R p1 = xr * ar;
+            R p2 = xi * ai;
+            R re = p1 - p2;
+            R p3 = ai * xr;
+            R p4 = xi * ar;
+            R im = p3 + p4;
+            x.t[2 * i] = re;
+            x.t[2 * i + 1] = im;
+        }
+        return x.v;
+    }
+};
+
+template <typename A>
+struct PatchAddReal {
+    static constexpr int kOps = 3, kIn = 2;
+    A al, be;
+    template <int W>
+    __device__ __forceinline__ typename Vec<W>::T apply(typename Vec<W>::T av, typename Vec<W>::T bv) const {
+        constexpr int N = W / (int)sizeof(A);
+        union { typename Vec<W>::T v; A t[N]; } a, b;
+        a.v = av;
+        b.v = bv;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            A p1 = al * a.t[i];
+            A p2 = be * b.t[i];
+            a.t[i] = p1 + p2;
+        }
+        return a.v;
+    }
+};
+
+// x = alpha, y = beta; a, b the elements (global.npatch.c:2537-2546), left to right
+template <typename R>
+struct PatchAddCplx {
+    static constexpr int kOps = 3, kIn = 2;
+    R xr, xi, yr, yi;
+    template <int W>
+    __device__ __forceinline__ typename Vec<W>::T apply(typename Vec<W>::T av, typename Vec<W>::T bv) const {
+        constexpr int N = W / (int)(2 * sizeof(R));
+        union { typename Vec<W>::T v; R t[2 * N]; } a, b;
+        a.v = av;
+        b.v = bv;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const R ar = a.t[2 * i], ai = a.t[2 * i + 1], br = b.t[2 * i], bi = b.t[2 * i + 1];
+            R p1 = xr * ar;
+            R p2 = xi * ai;
+            R p3 = yr * br;
+            R p4 = yi * bi;
+            R re = p1 - p2;
+            re = re + p3;
+            re = re - p4;
+            R q1 = xr * ai;
+            R q2 = xi * ar;
+            R q3 = yr * bi;
+            R q4 = yi * br;
+            R im = q1 + q2;
+            im = im + q3;
+            im = im + q4;
+            a.t[2 * i] = re;
+            a.t[2 * i + 1] = im;
+        }
+        return a.v;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// MAP kernel: block (x, y) = chunk x of row row0 + y
+template <class OP, int W, int U, int BS, int LV>
+__global__ __launch_bounds__(BS) void k_patch_map(const PatchDesc d, const OP op) {
+    typedef typename Vec<W>::T V;
+    int64_t off[OP::kOps];
+    patch_row<OP::kOps, LV>(d, d.row0 + blockIdx.y, off);
+    const uint64_t c0 = (uint64_t)blockIdx.x * (uint64_t)(BS * U);
+    const int64_t b0 = (int64_t)((c0 + threadIdx.x) * (uint64_t)W);
+    char *o = d.p[0] + off[0] + b0;
+    const char *i1 = o, *i2 = o;
+    if constexpr (OP::kIn == 2) {
+        i1 = d.p[1] + off[1] + b0;
+        i2 = d.p[2] + off[2] + b0;
+    }
+    V x[U], y[U];
+    if (c0 + (uint64_t)(BS * U) <= d.nvec) {   // wave-uniform: the whole chunk lies inside the row
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            if constexpr (OP::kIn >= 1) x[k] = vload<W, true>(i1 + (int64_t)k * BS * W);
+            else x[k] = V{};
+            if constexpr (OP::kIn == 2) y[k] = vload<W, true>(i2 + (int64_t)k * BS * W);
+            else y[k] = x[k];
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) vstore<W, true>(o + (int64_t)k * BS * W, op.template apply<W>(x[k], y[k]));
+        return;
+    }
+    for (int k = 0; k < U; ++k) {   // row tail: one vector at a time
+        if (c0 + threadIdx.x + (uint64_t)k * BS >= d.nvec) continue;
+        V a = V{}, b = V{};
+        if constexpr (OP::kIn >= 1) a = vload<W, true>(i1 + (int64_t)k * BS * W);
+        if constexpr (OP::kIn == 2) b = vload<W, true>(i2 + (int64_t)k * BS * W);
+        vstore<W, true>(o + (int64_t)k * BS * W, op.template apply<W>(a, b));
+    }
+}
+
+// ---------------------------------------------------------------------------
+// DOT kernels
+constexpr int kDotBS = 256;     // threads per workgroup (4 waves)
+constexpr int kDotItems = 8;    // (row, chunk) items per workgroup; a chunk is kDotBS vectors
+constexpr int kFinalPer = 4;    // consecutive partials per lane and pass of the final workgroup
+
+template <typename A>
+struct PatchDotReal {
+    typedef A acc_t;
+    static constexpr int kAcc = 1;
+    template <int W>
+    __device__ __forceinline__ static void accum(A (&acc)[1], typename Vec<W>::T av, typename Vec<W>::T bv) {
+        constexpr int N = W / (int)sizeof(A);
+        union { typename Vec<W>::T v; A t[N]; } a, b;
+        a.v = av;
+        b.v = bv;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            A p = a.t[i] * b.t[i];
+            acc[0] = acc[0] + p;
+        }
+    }
+};
+
+template <typename R>
+struct PatchDotCplx {
+    typedef R acc_t;
+    static constexpr int kAcc = 2;
+    template <int W>
+    __device__ __forceinline__ static void accum(R (&acc)[2], typename Vec<W>::T av, typename Vec<W>::T bv) {
+        constexpr int N = W / (int)(2 * sizeof(R));
+        union { typename Vec<W>::T v; R t[2 * N]; } a, b;
+        a.v = av;
+        b.v = bv;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const R ar = a.t[2 * i], ai = a.t[2 * i + 1], br = b.t[2 * i], bi = b.t[2 * i + 1];
+            R p1 = ar * br;
+            R p2 = bi * ai;
+            R re = p1 - p2;
+            acc[0] = acc[0] + re;
+            R p3 = ai * br;
+            R p4 = bi * ar;
+            R im = p3 + p4;
+            acc[1] = acc[1] + im;
+        }
+    }
+};
+
+template <typename A>
+__device__ __forceinline__ A shfl_down_any(A v, int delta) {
+    union { A a; int w[sizeof(A) / 4]; } u;
+    u.a = v;
+#pragma unroll
+    for (int i = 0; i < (int)(sizeof(A) / 4); ++i) u.w[i] = __shfl_down(u.w[i], delta, 64);
+    return u.a;
+}
+
+// one word of the result into mapped pinned host memory (as k_flag does)
+template <typename A>
+__device__ __forceinline__ void store_sys(A *p, A v) {
+    if constexpr (sizeof(A) == 4) {
+        uint32_t w;
+        memcpy(&w, &v, 4);
+        __hip_atomic_store(reinterpret_cast<uint32_t *>(p), w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    } else {
+        uint64_t w;
+        memcpy(&w, &v, 8);
+        __hip_atomic_store(reinterpret_cast<uint64_t *>(p), w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// the workgroup's sum in a fixed order: shuffle tree per wave, then waves 0..3 by lane 0
+template <typename A, int NA, bool SYS>
+__device__ __forceinline__ void block_sum_store(A (&acc)[NA], A *out) {
+    __shared__ A sh[kDotBS / 64][NA];
+#pragma unroll
+    for (int delta = 32; delta > 0; delta >>= 1) {
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const A o = shfl_down_any(acc[i], delta);
+            acc[i] = acc[i] + o;
+        }
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < NA; ++i) sh[wave][i] = acc[i];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            A s = sh[0][i];
+#pragma unroll
+            for (int w = 1; w < kDotBS / 64; ++w) s = s + sh[w][i];
+            if constexpr (SYS) store_sys(out + i, s);
+            else out[i] = s;
+        }
+    }
+}
+
+template <class OP, int W, int LV>
+__global__ __launch_bounds__(kDotBS) void k_patch_dot(const PatchDesc d, const uint32_t items, const FastDiv chunk_div,
+                                                      typename OP::acc_t *part) {
+    typedef typename Vec<W>::T V;
+    typedef typename OP::acc_t A;
+    V va[kDotItems], vb[kDotItems];
+    bool ok[kDotItems];
+    const uint32_t i0 = blockIdx.x * (uint32_t)kDotItems;
+    // every load first and without a branch, so that all are in flight together: a lane
+    // without a vector in an item (past the row's end, or an item past the last) reads
+    // vector 0 of a row of the patch instead and drops it below
+#pragma unroll
+    for (int k = 0; k < kDotItems; ++k) {
+        const bool in = i0 + k < items;
+        const uint32_t it = in ? i0 + k : 0u;
+        const uint32_t rl = chunk_div.div(it);
+        const uint32_t chunk = it - rl * chunk_div.d;
+        int64_t off[2];
+        patch_row<2, LV>(d, rl, off);
+        const uint64_t v = (uint64_t)chunk * kDotBS + threadIdx.x;
+        ok[k] = in && v < d.nvec;
+        const int64_t b = ok[k] ? (int64_t)(v * W) : 0;
+        va[k] = vload<W, true>(d.p[0] + off[0] + b);
+        vb[k] = vload<W, true>(d.p[1] + off[1] + b);
+    }
+    // the sums in item order; a dropped vector adds 0 * 0 = +0, which leaves every sum as
+    // it is (a sum that starts at +0 never becomes -0)
+    A acc[OP::kAcc] = {};
+#pragma unroll
+    for (int k = 0; k < kDotItems; ++k) {
+        if (!ok[k]) {
+            va[k] = V{};
+            vb[k] = V{};
+        }
+        OP::template accum<W>(acc, va[k], vb[k]);
+    }
+    block_sum_store<A, OP::kAcc, false>(acc, part + (size_t)blockIdx.x * OP::kAcc);
+}
+
+template <typename A, int NA>
+__global__ __launch_bounds__(kDotBS) void k_patch_dot_final(const A *part, const uint32_t n, A *out) {
+    A acc[NA] = {};
+    for (uint32_t base = 0; base < n; base += kDotBS * kFinalPer) {
+#pragma unroll
+        for (int k = 0; k < kFinalPer; ++k) {
+            const uint32_t i = base + threadIdx.x * kFinalPer + k;
+            if (i < n) {
+#pragma unroll
+                for (int j = 0; j < NA; ++j) acc[j] = acc[j] + part[(size_t)i * NA + j];
+            }
+        }
+    }
+    block_sum_store<A, NA, true>(acc, out);
+}
+
+// ---------------------------------------------------------------------------
+// host: checks, merging, vector width
+struct PatchPlan {
+    int esz = 0, W = 0, L = 0, block = 0;
+    uint64_t row_bytes = 0, rows = 1;
+    uint32_t cn[kPatchMaxLevels] = {};
+    int64_t st[3][kPatchMaxLevels] = {};
+};
+
+// 0: launch; 1: nothing to do (a count of zero); < 0: error
+static int patch_plan(int op, int nops, const void *const *base, const long long *const *stride,
+                      const long long *count, int ndim, PatchPlan &p) {
+    if (ndim < 1 || ndim > kPatchMaxLevels + 1) return kPatchErrNdim;
+    p.esz = (op == kOpCopy) ? 0 : elem_size(op);
+    if (!p.esz) return kPatchErrOp;
+    if (!count) return kPatchErrCount;
+    bool empty = false;
+    for (int d = 0; d < ndim; ++d) {
+        if (count[d] < 0) return kPatchErrCount;
+        if (count[d] == 0) empty = true;
+    }
+    for (int k = 0; k < nops; ++k)
+        if (ndim > 1 && !stride[k]) return kPatchErrStride;
+    if (empty) return 1;
+    if (count[0] > (long long)(INT64_MAX / 32)) return kPatchErrRange;
+    p.row_bytes = (uint64_t)count[0] * (uint64_t)p.esz;
+    int L = 0;
+    for (int d = 1; d < ndim; ++d) {
+        if (count[d] == 1) continue;
+        if (count[d] >= (1ll << 31)) return kPatchErrRange;
+        p.cn[L] = (uint32_t)count[d];
+        for (int k = 0; k < nops; ++k) p.st[k][L] = stride[k][d - 1];
+        ++L;
+    }
+    auto drop = [&](int j) {
+        for (int i = j; i + 1 < L; ++i) {
+            p.cn[i] = p.cn[i + 1];
+            for (int k = 0; k < nops; ++k) p.st[k][i] = p.st[k][i + 1];
+        }
+        --L;
+    };
+    // rows back to back on every operand: one longer row
+    while (L > 0) {
+        bool cont = true;
+        for (int k = 0; k < nops; ++k) cont = cont && p.st[k][0] == (int64_t)p.row_bytes;
+        if (!cont || p.row_bytes * p.cn[0] > (uint64_t)(INT64_MAX / 2)) break;
+        p.row_bytes *= p.cn[0];
+        drop(0);
+    }
+    // level j+1 continues level j on every operand: one level
+    for (int j = 0; j + 1 < L;) {
+        bool cont = (uint64_t)p.cn[j] * p.cn[j + 1] < (1ull << 31);
+        for (int k = 0; k < nops; ++k) cont = cont && p.st[k][j + 1] == p.st[k][j] * (int64_t)p.cn[j];
+        if (cont) {
+            p.cn[j] *= p.cn[j + 1];
+            drop(j + 1);
+        } else {
+            ++j;
+        }
+    }
+    p.L = L;
+    p.rows = 1;
+    for (int j = 0; j < L; ++j) p.rows *= p.cn[j];
+    if (p.rows >= (1ull << 31)) return kPatchErrRange;
+    // vector width: the largest power of two <= 16 dividing every base, stride and the row
+    uint64_t a = p.row_bytes | 16;
+    for (int k = 0; k < nops; ++k) {
+        a |= (uint64_t)(uintptr_t)base[k];
+        for (int j = 0; j < L; ++j) a |= (uint64_t)p.st[k][j];
+    }
+    int W = (int)lowbit(a);
+    // elements below their natural alignment: one element per vector at dword alignment
+    // (as launch_strided); below 4 bytes the launcher refuses
+    if (W < p.esz) {
+        if (W < 4) return kPatchErrAlign;
+        W = p.esz;
+    }
+    p.W = W;
+    // one-wave blocks when every row starts 4 KiB-aligned on every operand, else 128
+    // threads (launch_strided's choice for the rows kernels)
+    uint64_t al = 0;
+    for (int k = 0; k < nops; ++k) {
+        al |= (uint64_t)(uintptr_t)base[k];
+        for (int j = 0; j < L; ++j) al |= (uint64_t)p.st[k][j];
+    }
+    p.block = (W == 16 && !(al & 4095)) ? 64 : 128;
+    return 0;
+}
+
+// byte span [lo, hi) of operand k of a plan
+static void plan_span(const PatchPlan &p, int k, const void *base, int64_t &lo, int64_t &hi) {
+    lo = hi = (int64_t)(uintptr_t)base;
+    for (int j = 0; j < p.L; ++j) {
+        const int64_t ext = p.st[k][j] * (int64_t)(p.cn[j] - 1);
+        if (ext < 0) lo += ext;
+        else hi += ext;
+    }
+    hi += (int64_t)p.row_bytes;
+}
+
+// c may be exactly a (or b): the same base and the same strides; any other overlap of
+// c with an input is refused
+static bool add_overlap_ok(const PatchPlan &p, const void *const *base) {
+    int64_t clo, chi;
+    plan_span(p, 0, base[0], clo, chi);
+    for (int k = 1; k < 3; ++k) {
+        bool same = base[k] == base[0];
+        for (int j = 0; j < p.L; ++j) same = same && p.st[k][j] == p.st[0][j];
+        if (same) continue;
+        int64_t lo, hi;
+        plan_span(p, k, base[k], lo, hi);
+        if (lo < chi && clo < hi) return false;
+    }
+    return true;
+}
+
+static void fill_desc(PatchDesc &d, const PatchPlan &p, int nops, const void *const *base) {
+    memset(&d, 0, sizeof(d));
+    for (int k = 0; k < nops; ++k) {
+        d.p[k] = (char *)base[k];
+        for (int j = 0; j < p.L; ++j) d.str[k][j] = p.st[k][j];
+    }
+    for (int j = 0; j < kPatchMaxLevels; ++j) d.cnt[j] = make_fastdiv(j < p.L ? p.cn[j] : 1);   // stride 0 beyond L
+    d.levels = p.L;
+    d.nvec = p.row_bytes / (uint64_t)p.W;
+}
+
+template <class OP, int W, int BS, int U>
+static hipError_t go_map(PatchDesc d, const PatchPlan &p, const OP &op, hipStream_t st) {
+    const uint64_t chunks = (d.nvec + (uint64_t)(BS * U) - 1) / (uint64_t)(BS * U);
+    if (chunks > 0x7fffffffull) return hipErrorInvalidValue;
+    for (uint64_t r0 = 0; r0 < p.rows; r0 += 65535) {
+        const uint64_t nr = p.rows - r0 < 65535 ? p.rows - r0 : 65535;
+        d.row0 = (uint32_t)r0;
+        if (p.L <= 1)
+            hipLaunchKernelGGL((k_patch_map<OP, W, U, BS, 1>), dim3((unsigned)chunks, (unsigned)nr), dim3(BS), 0, st, d,
+                               op);
+        else
+            hipLaunchKernelGGL((k_patch_map<OP, W, U, BS, 0>), dim3((unsigned)chunks, (unsigned)nr), dim3(BS), 0, st, d,
+                               op);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// ELEM: bytes of one element (W >= ELEM always).  A store-only operation (fill) has no
+// loads to keep in flight: 256-thread blocks of 4 vectors per lane (16 KiB at W = 16).
+template <class OP, int ELEM>
+static hipError_t go_map_w(const PatchDesc &d, const PatchPlan &p, const OP &op, hipStream_t st) {
+    if constexpr (OP::kIn == 0) {
+        if (p.W == 16) return go_map<OP, 16, 256, 4>(d, p, op, st);
+        if (p.W == 8) return go_map<OP, 8, 256, 4>(d, p, op, st);
+        if (p.W == 4) return go_map<OP, 4, 256, 4>(d, p, op, st);
+        return hipErrorInvalidValue;
+    } else {
+        if (p.W == 16)
+            return p.block == 64 ? go_map<OP, 16, 64, 1>(d, p, op, st) : go_map<OP, 16, 128, 1>(d, p, op, st);
+        if constexpr (ELEM <= 8) {
+            if (p.W == 8) return go_map<OP, 8, 128, 2>(d, p, op, st);
+        }
+        if constexpr (ELEM <= 4) {
+            if (p.W == 4) return go_map<OP, 4, 128, 4>(d, p, op, st);
+        }
+        return hipErrorInvalidValue;
+    }
+}
+
+static int rc_of(hipError_t e) { return e == hipSuccess ? 0 : -100 - (int)e; }
+
+template <typename T> static T rd(const void *p, int i = 0) {
+    T v;
+    memcpy(&v, (const char *)p + (size_t)i * sizeof(T), sizeof(T));
+    return v;
+}
+
+int launch_patch_fill(int op, const void *value, void *dst, const long long *dst_stride, const long long *count,
+                      int ndim, hipStream_t stream) {
+    PatchPlan p;
+    const void *base[1] = {dst};
+    const long long *str[1] = {dst_stride};
+    const int rc = patch_plan(op, 1, base, str, count, ndim, p);
+    if (rc) return rc < 0 ? rc : 0;
+    if (!value) return kPatchErrScalar;
+    PatchDesc d;
+    fill_desc(d, p, 1, base);
+    PatchFill f;
+    for (int i = 0; i < 16; i += p.esz) memcpy((char *)&f.pat + i, value, (size_t)p.esz);
+    return rc_of(go_map_w<PatchFill, 4>(d, p, f, stream));
+}
+
+int launch_patch_scale(int op, const void *alpha, void *dst, const long long *dst_stride, const long long *count,
+                       int ndim, hipStream_t stream) {
+    PatchPlan p;
+    const void *base[1] = {dst};
+    const long long *str[1] = {dst_stride};
+    const int rc = patch_plan(op, 1, base, str, count, ndim, p);
+    if (rc) return rc < 0 ? rc : 0;
+    if (!alpha) return kPatchErrScalar;
+    PatchDesc d;
+    fill_desc(d, p, 1, base);
+    hipError_t e = hipErrorInvalidValue;
+    switch (op) {
+    case 37: e = go_map_w<PatchScaleReal<uint32_t>, 4>(d, p, PatchScaleReal<uint32_t>{rd<uint32_t>(alpha)}, stream); break;
+    case 38: e = go_map_w<PatchScaleReal<double>, 8>(d, p, PatchScaleReal<double>{rd<double>(alpha)}, stream); break;
+    case 39: e = go_map_w<PatchScaleReal<float>, 4>(d, p, PatchScaleReal<float>{rd<float>(alpha)}, stream); break;
+    case 40:
+        e = go_map_w<PatchScaleCplx<float>, 8>(d, p, PatchScaleCplx<float>{rd<float>(alpha), rd<float>(alpha, 1)}, stream);
+        break;
+    case 41:
+        e = go_map_w<PatchScaleCplx<double>, 16>(d, p, PatchScaleCplx<double>{rd<double>(alpha), rd<double>(alpha, 1)},
+                                                 stream);
+        break;
+    case 42: e = go_map_w<PatchScaleReal<uint64_t>, 8>(d, p, PatchScaleReal<uint64_t>{rd<uint64_t>(alpha)}, stream); break;
+    }
+    return rc_of(e);
+}
+
+// the checks of launch_patch_add without a launch (no device needed); plan[0..3] =
+// {vector width, row levels after merging, rows, vectors per row}
+int plan_patch_add(int op, const void *a, const long long *a_stride, const void *b, const long long *b_stride,
+                   const void *c, const long long *c_stride, const long long *count, int ndim, long long plan[4],
+                   PatchPlan *out) {
+    PatchPlan p;
+    const void *base[3] = {c, a, b};
+    const long long *str[3] = {c_stride, a_stride, b_stride};
+    if (plan) plan[0] = plan[1] = plan[2] = plan[3] = 0;
+    const int rc = patch_plan(op, 3, base, str, count, ndim, p);
+    if (rc) return rc;
+    if (!add_overlap_ok(p, base)) return kPatchErrOverlap;
+    if (plan) {
+        plan[0] = p.W;
+        plan[1] = p.L;
+        plan[2] = (long long)p.rows;
+        plan[3] = (long long)(p.row_bytes / (uint64_t)p.W);
+    }
+    if (out) *out = p;
+    return 0;
+}
+
+int launch_patch_add(int op, const void *alpha, const void *a, const long long *a_stride, const void *beta,
+                     const void *b, const long long *b_stride, void *c, const long long *c_stride,
+                     const long long *count, int ndim, hipStream_t stream) {
+    PatchPlan p;
+    const int rc = plan_patch_add(op, a, a_stride, b, b_stride, c, c_stride, count, ndim, nullptr, &p);
+    if (rc) return rc < 0 ? rc : 0;
+    if (!alpha || !beta) return kPatchErrScalar;
+    const void *base[3] = {c, a, b};
+    PatchDesc d;
+    fill_desc(d, p, 3, base);
+    hipError_t e = hipErrorInvalidValue;
+    switch (op) {
+    case 37:
+        e = go_map_w<PatchAddReal<uint32_t>, 4>(d, p, PatchAddReal<uint32_t>{rd<uint32_t>(alpha), rd<uint32_t>(beta)},
+                                                stream);
+        break;
+    case 38:
+        e = go_map_w<PatchAddReal<double>, 8>(d, p, PatchAddReal<double>{rd<double>(alpha), rd<double>(beta)}, stream);
+        break;
+    case 39:
+        e = go_map_w<PatchAddReal<float>, 4>(d, p, PatchAddReal<float>{rd<float>(alpha), rd<float>(beta)}, stream);
+        break;
+    case 40:
+        e = go_map_w<PatchAddCplx<float>, 8>(
+            d, p, PatchAddCplx<float>{rd<float>(alpha), rd<float>(alpha, 1), rd<float>(beta), rd<float>(beta, 1)}, stream);
+        break;
+    case 41:
+        e = go_map_w<PatchAddCplx<double>, 16>(
+            d, p, PatchAddCplx<double>{rd<double>(alpha), rd<double>(alpha, 1), rd<double>(beta), rd<double>(beta, 1)},
+            stream);
+        break;
+    case 42:
+        e = go_map_w<PatchAddReal<uint64_t>, 8>(d, p, PatchAddReal<uint64_t>{rd<uint64_t>(alpha), rd<uint64_t>(beta)},
+                                                stream);
+        break;
+    }
+    return rc_of(e);
+}
+
+// ---------------------------------------------------------------------------
+// dot: per-thread scratch (the partials in HBM, the result in mapped pinned memory),
+// grown on demand, freed by patch_release() at comex_finalize
+struct DotScratch {
+    int dev = -1;
+    void *part = nullptr;
+    size_t part_bytes = 0;
+    void *res_host = nullptr, *res_dev = nullptr;
+};
+static std::mutex g_dot_mu;
+static std::vector<DotScratch *> g_dot_all;
+static thread_local DotScratch *t_dot = nullptr;
+
+static void dot_scratch_free(DotScratch &s) {
+    if (s.part) (void)hipFree(s.part);
+    if (s.res_host) (void)hipHostFree(s.res_host);
+    s = DotScratch();
+}
+
+void patch_release() {
+    std::lock_guard<std::mutex> g(g_dot_mu);
+    for (DotScratch *s : g_dot_all) dot_scratch_free(*s);
+}
+
+static DotScratch *dot_scratch(size_t bytes) {
+    if (!t_dot) {
+        t_dot = new DotScratch();
+        std::lock_guard<std::mutex> g(g_dot_mu);
+        g_dot_all.push_back(t_dot);
+    }
+    std::lock_guard<std::mutex> g(g_dot_mu);
+    DotScratch &s = *t_dot;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    if (s.dev != dev) dot_scratch_free(s);
+    s.dev = dev;
+    if (!s.res_host) {
+        if (hipHostMalloc(&s.res_host, 16, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) return nullptr;
+        if (hipHostGetDevicePointer(&s.res_dev, s.res_host, 0) != hipSuccess) return nullptr;
+    }
+    if (s.part_bytes < bytes) {
+        if (s.part) (void)hipFree(s.part);
+        s.part = nullptr;
+        s.part_bytes = 0;
+        size_t want = 1 << 16;
+        while (want < bytes) want <<= 1;
+        if (hipMalloc(&s.part, want) != hipSuccess) return nullptr;
+        s.part_bytes = want;
+    }
+    return &s;
+}
+
+template <class OP, int W>
+static hipError_t go_dot(const PatchDesc &d, uint32_t items, FastDiv chunk_div, uint32_t nwg, DotScratch *s,
+                         hipStream_t st) {
+    typedef typename OP::acc_t A;
+    if (d.levels <= 1)
+        hipLaunchKernelGGL((k_patch_dot<OP, W, 1>), dim3(nwg), dim3(kDotBS), 0, st, d, items, chunk_div, (A *)s->part);
+    else
+        hipLaunchKernelGGL((k_patch_dot<OP, W, 0>), dim3(nwg), dim3(kDotBS), 0, st, d, items, chunk_div, (A *)s->part);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_patch_dot_final<A, OP::kAcc>), dim3(1), dim3(kDotBS), 0, st, (const A *)s->part, nwg,
+                       (A *)s->res_dev);
+    return hipGetLastError();
+}
+
+template <class OP, int ELEM>
+static hipError_t go_dot_w(int W, const PatchDesc &d, uint32_t items, FastDiv cd, uint32_t nwg, DotScratch *s,
+                           hipStream_t st) {
+    if (W == 16) return go_dot<OP, 16>(d, items, cd, nwg, s, st);
+    if constexpr (ELEM <= 8) {
+        if (W == 8) return go_dot<OP, 8>(d, items, cd, nwg, s, st);
+    }
+    if constexpr (ELEM <= 4) {
+        if (W == 4) return go_dot<OP, 4>(d, items, cd, nwg, s, st);
+    }
+    return hipErrorInvalidValue;
+}
+
+int launch_patch_dot(int op, const void *a, const long long *a_stride, const void *b, const long long *b_stride,
+                     const long long *count, int ndim, void *result, hipStream_t stream) {
+    PatchPlan p;
+    const void *base[2] = {a, b};
+    const long long *str[2] = {a_stride, b_stride};
+    const int rc = patch_plan(op, 2, base, str, count, ndim, p);
+    if (rc < 0) return rc;
+    if (!result) return kPatchErrScalar;
+    if (rc == 1) {   // an empty patch: the sum of nothing
+        memset(result, 0, (size_t)p.esz);
+        return 0;
+    }
+    PatchDesc d;
+    fill_desc(d, p, 2, base);
+    const uint64_t chunks = (d.nvec + kDotBS - 1) / kDotBS;
+    const uint64_t items = chunks * p.rows;
+    if (chunks >= (1ull << 31) || items >= (1ull << 31)) return kPatchErrRange;
+    const uint32_t nwg = (uint32_t)((items + kDotItems - 1) / kDotItems);
+    DotScratch *s = dot_scratch((size_t)nwg * 16);
+    if (!s) return -100 - (int)hipGetLastError();
+    const FastDiv cd = make_fastdiv((uint32_t)chunks);
+    hipError_t e = hipErrorInvalidValue;
+    switch (op) {
+    case 37: e = go_dot_w<PatchDotReal<uint32_t>, 4>(p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
+    case 38: e = go_dot_w<PatchDotReal<double>, 8>(p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
+    case 39: e = go_dot_w<PatchDotReal<float>, 4>(p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
+    case 40: e = go_dot_w<PatchDotCplx<float>, 8>(p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
+    case 41: e = go_dot_w<PatchDotCplx<double>, 16>(p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
+    case 42: e = go_dot_w<PatchDotReal<uint64_t>, 8>(p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
+    }
+    if (e != hipSuccess) return rc_of(e);
+    e = stream ? hipStreamSynchronize(stream) : hipDeviceSynchronize();
+    if (e != hipSuccess) return rc_of(e);
+    memcpy(result, s->res_host, (size_t)p.esz);
+    return 0;
+}
+
+}  // namespace gaamd

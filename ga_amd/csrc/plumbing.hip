@@ -74,6 +74,33 @@ int gaamd_plan_strided(int op, const void *src, const int *src_stride, const voi
     return rc;
 }
 
+int gaamd_patch_fill(int op, const void *value, void *dst, const long long *dst_stride, const long long *count,
+                     int ndim, void *stream) {
+    return launch_patch_fill(op, value, dst, dst_stride, count, ndim, stream_of(stream));
+}
+
+int gaamd_patch_scale(int op, const void *alpha, void *dst, const long long *dst_stride, const long long *count,
+                      int ndim, void *stream) {
+    return launch_patch_scale(op, alpha, dst, dst_stride, count, ndim, stream_of(stream));
+}
+
+int gaamd_patch_add(int op, const void *alpha, const void *a, const long long *a_stride, const void *beta,
+                    const void *b, const long long *b_stride, void *c, const long long *c_stride,
+                    const long long *count, int ndim, void *stream) {
+    return launch_patch_add(op, alpha, a, a_stride, beta, b, b_stride, c, c_stride, count, ndim, stream_of(stream));
+}
+
+int gaamd_patch_dot(int op, const void *a, const long long *a_stride, const void *b, const long long *b_stride,
+                    const long long *count, int ndim, void *result, void *stream) {
+    return launch_patch_dot(op, a, a_stride, b, b_stride, count, ndim, result, stream_of(stream));
+}
+
+int gaamd_patch_add_plan(int op, const void *a, const long long *a_stride, const void *b, const long long *b_stride,
+                         const void *c, const long long *c_stride, const long long *count, int ndim,
+                         long long plan[4]) {
+    return plan_patch_add(op, a, a_stride, b, b_stride, c, c_stride, count, ndim, plan);
+}
+
 long gaamd_packed_size(const int *count, int stride_levels) {
     long n = count[0];
     for (int j = 1; j <= stride_levels; ++j) n *= count[j];

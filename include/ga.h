@@ -83,6 +83,46 @@ void NGA_Access(int g_a, int lo[], int hi[], void *ptr, int ld[]);
 void NGA_Release(int g_a, int lo[], int hi[]);
 void NGA_Release_update(int g_a, int lo[], int hi[]);
 
+/* Computing on arrays where they lie (capi.c:1645-1880, 2375, 2748, 3574-3990,
+   4163-4250 -> global/src/global.npatch.c, global.nalg.c).  Collective, with the
+   reference's syncs on entry and exit; each rank runs one gfx950 kernel on its own
+   part of the patch (ga_amd.h gaamd_patch_*), the reference's arithmetic expression
+   for expression.  The dot products end in a sum over ranks: every rank returns the
+   same bits, and the same arrays give the same bits on every call.  Arrays of equal
+   block maps with equal patches are computed in place; any other combination goes
+   through a GA_Duplicate temporary and NGA_Copy_patch, as in the reference.
+   Transposed patches (trans / t_a / t_b other than 'N'), patches of different rank or
+   extents, a type that does not match the call, and arrays in a host segment abort
+   through GA_Error. */
+int GA_Duplicate(int g_a, char *array_name);
+int GA_Compare_distr(int g_a, int g_b);   /* 0: same shape and block maps */
+void NGA_Inquire(int g_a, int *type, int *ndim, int dims[]);
+void GA_Fill(int g_a, void *value);
+void GA_Scale(int g_a, void *value);
+void GA_Add(void *alpha, int g_a, void *beta, int g_b, int g_c);
+void GA_Copy(int g_a, int g_b);
+int GA_Idot(int g_a, int g_b);
+long GA_Ldot(int g_a, int g_b);
+float GA_Fdot(int g_a, int g_b);
+double GA_Ddot(int g_a, int g_b);
+SingleComplex GA_Cdot(int g_a, int g_b);
+DoubleComplex GA_Zdot(int g_a, int g_b);
+void NGA_Fill_patch(int g_a, int lo[], int hi[], void *val);
+void NGA_Zero_patch(int g_a, int lo[], int hi[]);
+void NGA_Scale_patch(int g_a, int lo[], int hi[], void *alpha);
+void NGA_Add_patch(void *alpha, int g_a, int alo[], int ahi[], void *beta, int g_b, int blo[], int bhi[],
+                   int g_c, int clo[], int chi[]);
+void NGA_Copy_patch(char trans, int g_a, int alo[], int ahi[], int g_b, int blo[], int bhi[]);
+int NGA_Idot_patch(int g_a, char t_a, int alo[], int ahi[], int g_b, char t_b, int blo[], int bhi[]);
+long NGA_Ldot_patch(int g_a, char t_a, int alo[], int ahi[], int g_b, char t_b, int blo[], int bhi[]);
+float NGA_Fdot_patch(int g_a, char t_a, int alo[], int ahi[], int g_b, char t_b, int blo[], int bhi[]);
+double NGA_Ddot_patch(int g_a, char t_a, int alo[], int ahi[], int g_b, char t_b, int blo[], int bhi[]);
+SingleComplex NGA_Cdot_patch(int g_a, char t_a, int alo[], int ahi[], int g_b, char t_b, int blo[], int bhi[]);
+DoubleComplex NGA_Zdot_patch(int g_a, char t_a, int alo[], int ahi[], int g_b, char t_b, int blo[], int bhi[]);
+/* global arrays alive on this rank (temporaries of the general path are destroyed
+   before their call returns) */
+int gaamd_ga_live_arrays(void);
+
 /* process grid the REGULAR distribution chose, C order (ga.h GA_Get_proc_grid) */
 void GA_Get_proc_grid(int g_a, int dims[]);
 /* process grid (C order) that NGA_Create picks for npes ranks (restated

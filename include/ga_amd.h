@@ -66,6 +66,33 @@ int gaamd_wire_selftest(int rounds);
 int gaamd_strided(int op, const void *scale, const void *src, const int *src_stride,
                   void *dst, const int *dst_stride, const int *count, int stride_levels,
                   void *stream);
+/* Computing on a patch where it lies (HBM): the loops of global/src/global.npatch.c
+ * (fill 1528-1650, scale 1953-1986, add 2520-2546, dot 938-1095), expression for
+ * expression, no FMA, integers in unsigned arithmetic.
+ * element type by COMEX_ACC_* code; count[] in ELEMENTS per dimension (dim 0 contiguous),
+ * *_stride[j] = byte stride of dimension j+1, ndim 1..7, all 64-bit.
+ * Negative codes, nothing launched: -2 ndim outside 1..7, -3 a negative count, -4 an
+ * unknown op, -5 a missing scalar or result, -6 missing strides, -7 2^31 rows or more
+ * after merging, -8 a base or stride below 4-byte alignment, -11 (add) c overlaps a or b
+ * without being exactly it (same base, same strides).  A count of zero: 0, no launch.
+ * gaamd_patch_dot synchronises its stream and writes one element to `result` (host
+ * memory); the same input gives the same bits on every run. */
+int gaamd_patch_fill (int op, const void *value, void *dst, const long long *dst_stride,
+                      const long long *count, int ndim, void *stream);
+int gaamd_patch_scale(int op, const void *alpha, void *dst, const long long *dst_stride,
+                      const long long *count, int ndim, void *stream);
+int gaamd_patch_add  (int op, const void *alpha, const void *a, const long long *a_stride,
+                      const void *beta,  const void *b, const long long *b_stride,
+                      void *c, const long long *c_stride, const long long *count, int ndim, void *stream);
+int gaamd_patch_dot  (int op, const void *a, const long long *a_stride, const void *b,
+                      const long long *b_stride, const long long *count, int ndim,
+                      void *result /* host, one element of the type */, void *stream);
+/* gaamd_patch_add's checks without a launch (no GPU needed): 0 it would launch, 1 nothing
+ * to do, or its error code; plan[0..3] = {vector width, row levels after merging, rows,
+ * vectors per row} */
+int gaamd_patch_add_plan(int op, const void *a, const long long *a_stride, const void *b,
+                         const long long *b_stride, const void *c, const long long *c_stride,
+                         const long long *count, int ndim, long long plan[4]);
 long gaamd_packed_size(const int *count, int stride_levels);
 int gaamd_pack(const void *src, const int *src_stride, const int *count, int stride_levels,
                void *packed, void *stream);
