@@ -192,6 +192,29 @@ def patch_add_plan(op, a, a_stride, b, b_stride, c, c_stride, count):
     return rc, {"width": out[0], "levels": out[1], "rows": out[2], "nvec": out[3]}
 
 
+def _trans(t):
+    return ord(t) if isinstance(t, (str, bytes)) else int(t)
+
+
+# row-major GEMM on the matrix cores (gaamd_gemm): a, b, c are device addresses, ld in
+# elements; scalars of None reach the library as NULL; the return code is handed back
+def gemm(op, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, stream=None):
+    ka, ap = scale_buffer(op, alpha) if alpha is not None else (None, None)
+    kb, bp = scale_buffer(op, beta) if beta is not None else (None, None)
+    return lib().gaamd_gemm(op, _trans(transa), _trans(transb), m, n, k, ap, ctypes.c_void_p(a), lda,
+                            ctypes.c_void_p(b), ldb, bp, ctypes.c_void_p(c), ldc, stream)
+
+
+def gemm_plan(op, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc):
+    """gaamd_gemm's checks without a launch (no GPU): (code, {tm, tn, tk, grid_m, grid_n, ksteps})"""
+    ka, ap = scale_buffer(op, alpha) if alpha is not None else (None, None)
+    kb, bp = scale_buffer(op, beta) if beta is not None else (None, None)
+    out = (ctypes.c_longlong * 6)()
+    rc = lib().gaamd_gemm_plan(op, _trans(transa), _trans(transb), m, n, k, ap, ctypes.c_void_p(a), lda,
+                               ctypes.c_void_p(b), ldb, bp, ctypes.c_void_p(c), ldc, out)
+    return rc, {"tm": out[0], "tn": out[1], "tk": out[2], "grid_m": out[3], "grid_n": out[4], "ksteps": out[5]}
+
+
 def last_launch():
     k, w, u, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     b = ctypes.c_ulonglong()

@@ -273,6 +273,14 @@ SIGNATURES = {
                                        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "gaamd_patch_add_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, c_ll_p, ctypes.c_void_p, c_ll_p,
                                             ctypes.c_void_p, c_ll_p, c_ll_p, ctypes.c_int, c_ll_p]),
+    "gaamd_gemm": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong,
+                                  ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+                                  ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_longlong, ctypes.c_void_p]),
+    "gaamd_gemm_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
+                                       ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_longlong, c_ll_p]),
     "gaamd_packed_size": (ctypes.c_long, [c_int_p, ctypes.c_int]),
     "gaamd_pack": (ctypes.c_int, [ctypes.c_void_p, c_int_p, c_int_p, ctypes.c_int, ctypes.c_void_p,
                                   ctypes.c_void_p]),
@@ -391,6 +399,14 @@ GA_SIGNATURES = {
     **{f"NGA_{n}dot_patch": (t, [ctypes.c_int, ctypes.c_char, c_int_p, c_int_p, ctypes.c_int, ctypes.c_char,
                                  c_int_p, c_int_p]) for n, t in _DOT_TYPES.items()},
     "gaamd_ga_live_arrays": (ctypes.c_int, []),
+    # matrix multiply
+    "GA_Dgemm": (None, [ctypes.c_char, ctypes.c_char, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                        ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int]),
+    "GA_Sgemm": (None, [ctypes.c_char, ctypes.c_char, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                        ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int]),
+    "NGA_Matmul_patch": (None, [ctypes.c_char, ctypes.c_char, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                c_int_p, c_int_p, ctypes.c_int, c_int_p, c_int_p, ctypes.c_int, c_int_p, c_int_p]),
+    "gaamd_ga_gemm_panel": (ctypes.c_int, []),
 }
 SIGNATURES.update(GA_SIGNATURES)
 

@@ -84,7 +84,7 @@ static struct {
     long numacc = 0, numput = 0, numget = 0, numsca = 0, numgat = 0;
     double acctot = 0, accloc = 0, scatot = 0, scaloc = 0, gattot = 0, gatloc = 0;
     // calls that compute on the arrays where they lie, and the bytes this rank's kernels moved
-    long numfill = 0, numscale = 0, numadd = 0, numcopy = 0, numdot = 0;
+    long numfill = 0, numscale = 0, numadd = 0, numcopy = 0, numdot = 0, numgemm = 0;
     double mathloc = 0;
 } g_stat;
 
@@ -1279,10 +1279,133 @@ GAAMD_DOT(SingleComplex, Cdot, C_SCPL)
 GAAMD_DOT(DoubleComplex, Zdot, C_DCPL)
 #undef GAAMD_DOT
 
+// ---- GA_Dgemm / GA_Sgemm / NGA_Matmul_patch ----------------------------------------
+// pnga_matmul (global/src/matmul.c) gets chunks of A and B to host buffers, multiplies
+// them with a host BLAS and accumulates the products into C.  Here every block is in HBM
+// and the owner computes: a rank cuts the C patch by its own block and, for every panel of
+// kGemmPanel values of k -- counted from the start of the patch's k range, never from a
+// block boundary -- gets the rows of op(A) and the columns of op(B) that part needs into
+// two HBM scratch buffers (NGA_Get's path: one strided copy kernel per owner, peers read
+// through their mappings) and runs gaamd_gemm into its block in place: the caller's beta
+// on the first panel, beta = 1 on the later ones.  The panels and the kernel's summation
+// order depend on neither the block maps nor the rank count, so neither do the bits of C.
+constexpr long kGemmPanel = 1024;
+
+static bool is_trans(char t, const char *what) {
+    if (t == 'n' || t == 'N') return false;
+    if (t == 't' || t == 'T') return true;
+    fatal("%s: trans '%c' is not one of N n T t", what, t);
+}
+
+static bool patches_meet(const long *alo, const long *ahi, const long *blo, const long *bhi) {
+    return alo[0] <= bhi[0] && blo[0] <= ahi[0] && alo[1] <= bhi[1] && blo[1] <= ahi[1];
+}
+
+// patches in Fortran order, 1-based: index 0 runs along a stored row (the C column
+// subscript), index 1 down the rows.  type: the array type the call is for, 0 = either.
+static void matmul_patch(int type, char transa, char transb, const void *alpha, const void *beta, int g_a,
+                         const long *alo, const long *ahi, int g_b, const long *blo, const long *bhi, int g_c,
+                         const long *clo, const long *chi, const char *what) {
+    GArray &a = arr(g_a), &b = arr(g_b), &c = arr(g_c);
+    const bool ta = is_trans(transa, what), tb = is_trans(transb, what);
+    if (c.type != C_DBL && c.type != C_FLOAT) fatal("%s: type %d is neither C_DBL nor C_FLOAT", what, c.type);
+    if (a.type != c.type || b.type != c.type) fatal("%s: types of the arrays differ", what);
+    if (type && c.type != type)
+        fatal("%s: type mismatch: arrays of type %d in a call for type %d", what, c.type, type);
+    if (a.ndim != 2 || b.ndim != 2 || c.ndim != 2) fatal("%s: arrays of rank other than 2 are not supported", what);
+    if (!alpha || !beta) fatal("%s: alpha or beta is missing", what);
+    need_hbm(a, what);
+    need_hbm(b, what);
+    need_hbm(c, what);
+    check_patch(a, alo, ahi, what);
+    check_patch(b, blo, bhi, what);
+    check_patch(c, clo, chi, what);
+    // op(A) is m x k, op(B) is k x n, C is m x n (matmul.c:1376-1381)
+    const long arows = ahi[1] - alo[1] + 1, acols = ahi[0] - alo[0] + 1;
+    const long brows = bhi[1] - blo[1] + 1, bcols = bhi[0] - blo[0] + 1;
+    const long m = ta ? acols : arows, k = ta ? arows : acols, kb = tb ? bcols : brows, n = tb ? brows : bcols;
+    if (kb != k || chi[1] - clo[1] + 1 != m || chi[0] - clo[0] + 1 != n)
+        fatal("%s: patch extents do not agree: op(A) is %ld x %ld, op(B) %ld x %ld, C %ld x %ld", what, m, k, kb, n,
+              chi[1] - clo[1] + 1, chi[0] - clo[0] + 1);
+    // every owner writes its part of C while others still read A and B
+    if ((g_c == g_a && patches_meet(clo, chi, alo, ahi)) || (g_c == g_b && patches_meet(clo, chi, blo, bhi)))
+        fatal("%s: the C patch overlaps an input patch of the same array", what);
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_stat.numgemm++;
+    const Sub sc = own_sub(c, clo, chi);
+    if (sc.any) {
+        const long mi = (long)sc.count[1], nj = (long)sc.count[0];       // this rank's rows and columns of C
+        const long i0 = sc.plo[1] - clo[1], j0 = sc.plo[0] - clo[0];     // ... from the patch's corner
+        const long kmax = std::min(k, kGemmPanel);
+        void *pa = gaamd_dev_malloc((size_t)mi * kmax * c.elemsize), *pb = gaamd_dev_malloc((size_t)kmax * nj * c.elemsize);
+        if (!pa || !pb) fatal("%s: no device memory for the panel buffers", what);
+        const double one_d = 1.0;
+        const float one_f = 1.0f;
+        const void *one = c.type == C_DBL ? (const void *)&one_d : (const void *)&one_f;
+        for (long kp = 0; kp < k; kp += kGemmPanel) {
+            const long kl = std::min(kGemmPanel, k - kp);
+            long lo[2], hi[2], ld[1];
+            // rows i0 .. i0 + mi of op(A), columns kp .. kp + kl: stored mi x kl, or kl x mi for 'T'
+            lo[0] = alo[0] + (ta ? i0 : kp);
+            hi[0] = lo[0] + (ta ? mi : kl) - 1;
+            lo[1] = alo[1] + (ta ? kp : i0);
+            hi[1] = lo[1] + (ta ? kl : mi) - 1;
+            const long lda = ld[0] = hi[0] - lo[0] + 1;
+            patch_op(GA_GET, g_a, lo, hi, pa, ld, nullptr);
+            // rows kp .. kp + kl of op(B), columns j0 .. j0 + nj: stored kl x nj, or nj x kl for 'T'
+            lo[0] = blo[0] + (tb ? kp : j0);
+            hi[0] = lo[0] + (tb ? kl : nj) - 1;
+            lo[1] = blo[1] + (tb ? j0 : kp);
+            hi[1] = lo[1] + (tb ? nj : kl) - 1;
+            const long ldb = ld[0] = hi[0] - lo[0] + 1;
+            patch_op(GA_GET, g_b, lo, hi, pb, ld, nullptr);
+            const int rc = gaamd_gemm(c.optype, transa, transb, mi, nj, kl, alpha, pa, lda, pb, ldb, kp ? one : beta,
+                                      sc.p, sc.ext[0], gaamd_stream());
+            if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+            // the next panel's gets overwrite the buffers
+            if (gaamd_sync(gaamd_stream()) != 0) fatal("%s: the stream failed", what);
+            g_stat.mathloc += (double)c.elemsize * ((double)mi * kl + (double)kl * nj + 2.0 * mi * nj);
+        }
+        gaamd_dev_free(pa);
+        gaamd_dev_free(pb);
+    }
+    math_end(what);
+}
+
+static void c_gemm(int type, char ta, char tb, int m, int n, int k, const void *alpha, int g_a, int g_b,
+                   const void *beta, int g_c, const char *what) {
+    // the leading corners, as stored: A m x k (k x m for 'T'), B k x n (n x k), C m x n
+    const bool tra = is_trans(ta, what), trb = is_trans(tb, what);
+    const long one[2] = {1, 1};
+    const long ah[2] = {tra ? m : k, tra ? k : m}, bh[2] = {trb ? k : n, trb ? n : k}, ch[2] = {n, m};
+    matmul_patch(type, ta, tb, alpha, beta, g_a, one, ah, g_b, one, bh, g_c, one, ch, what);
+}
+
+void GA_Dgemm(char ta, char tb, int m, int n, int k, double alpha, int g_a, int g_b, double beta, int g_c) {
+    c_gemm(C_DBL, ta, tb, m, n, k, &alpha, g_a, g_b, &beta, g_c, "GA_Dgemm");
+}
+void GA_Sgemm(char ta, char tb, int m, int n, int k, float alpha, int g_a, int g_b, float beta, int g_c) {
+    c_gemm(C_FLOAT, ta, tb, m, n, k, &alpha, g_a, g_b, &beta, g_c, "GA_Sgemm");
+}
+void NGA_Matmul_patch(char transa, char transb, void *alpha, void *beta, int g_a, int alo[], int ahi[], int g_b,
+                      int blo[], int bhi[], int g_c, int clo[], int chi[]) {
+    long l[3][GA_MAX_DIM], h[3][GA_MAX_DIM];
+    const int g[3] = {g_a, g_b, g_c};
+    int *lo[3] = {alo, blo, clo}, *hi[3] = {ahi, bhi, chi};
+    for (int i = 0; i < 3; i++) {
+        if (arr(g[i]).ndim != 2) fatal("NGA_Matmul_patch: arrays of rank other than 2 are not supported");
+        c2f_index(2, lo[i], l[i]);
+        c2f_index(2, hi[i], h[i]);
+    }
+    matmul_patch(0, transa, transb, alpha, beta, g_a, l[0], h[0], g_b, l[1], h[1], g_c, l[2], h[2], "NGA_Matmul_patch");
+}
+int gaamd_ga_gemm_panel(void) { return (int)kGemmPanel; }
+
 void GA_Print_stats(void) {
-    printf("[%d] GA on-device calls: fill %ld, scale %ld, add %ld, copy %ld, dot %ld; local bytes moved %.0f\n",
+    printf("[%d] GA on-device calls: fill %ld, scale %ld, add %ld, copy %ld, dot %ld; local bytes moved %.0f; "
+           "gemm %ld\n",
            my_rank(), g_stat.numfill, g_stat.numscale, g_stat.numadd, g_stat.numcopy, g_stat.numdot,
-           g_stat.mathloc);
+           g_stat.mathloc, g_stat.numgemm);
     printf("[%d] GA statistics: acc calls %ld, put calls %ld, get calls %ld, scatter calls %ld, gather calls %ld\n",
            my_rank(), g_stat.numacc, g_stat.numput, g_stat.numget, g_stat.numsca, g_stat.numgat);
     printf("[%d] accumulate bytes total %.0f, local %.0f (%.1f%%)\n", my_rank(), g_stat.acctot, g_stat.accloc,

@@ -8,3 +8,4 @@
 #include "gaamd_iov.hip"
 #include "gaamd_misc.hip"
 #include "gaamd_patch.hip"
+#include "gaamd_gemm.hip"

@@ -141,6 +141,21 @@ int plan_patch_add(int op, const void *a, const long long *a_stride, const void 
                    PatchPlan *out = nullptr);
 void patch_release();   // comex_finalize: every thread's dot-product scratch (streams idle)
 
+// ---- row-major GEMM on the matrix cores (gaamd_gemm.hip; ga_amd.h gaamd_gemm) ---------
+// op = COMEX_ACC_DBL or COMEX_ACC_FLT; ld in elements; the codes are the patch codes above
+// (kPatchErrCount a negative extent, kPatchErrOp the op or a trans, kPatchErrScalar,
+// kPatchErrStride an ld below the stored row, kPatchErrAlign, kPatchErrOverlap,
+// kPatchErrRange 2^31 tiles or more).
+constexpr int kGemmTM = 128, kGemmTN = 128, kGemmTK = 16;   // the workgroup's tile of C and its k step
+int launch_gemm(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
+                const void *a, long long lda, const void *b, long long ldb, const void *beta, void *c, long long ldc,
+                hipStream_t stream);
+// launch_gemm's checks without a launch (no device): 0 launch, 1 nothing to do (m or n is 0),
+// < 0 error; plan[0..5] = {tile M, tile N, tile K, tiles along m, tiles along n, k steps}
+int plan_gemm(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
+              const void *a, long long lda, const void *b, long long ldb, const void *beta, const void *c,
+              long long ldc, long long plan[6]);
+
 // comex_rmw: fetch-and-add (swap == 0) or swap of one 4- or 8-byte word at
 // `addr` (device-accessible); the old value lands in *out_dev (8 bytes)
 int launch_rmw(int swap, void *addr, int bytes, uint64_t val, uint64_t *out_dev, hipStream_t stream);

@@ -101,6 +101,18 @@ int gaamd_patch_add_plan(int op, const void *a, const long long *a_stride, const
     return plan_patch_add(op, a, a_stride, b, b_stride, c, c_stride, count, ndim, plan);
 }
 
+int gaamd_gemm(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
+               const void *a, long long lda, const void *b, long long ldb, const void *beta, void *c, long long ldc,
+               void *stream) {
+    return launch_gemm(op, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, stream_of(stream));
+}
+
+int gaamd_gemm_plan(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
+                    const void *a, long long lda, const void *b, long long ldb, const void *beta, const void *c,
+                    long long ldc, long long plan[6]) {
+    return plan_gemm(op, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, plan);
+}
+
 long gaamd_packed_size(const int *count, int stride_levels) {
     long n = count[0];
     for (int j = 1; j <= stride_levels; ++j) n *= count[j];

@@ -119,6 +119,38 @@ float NGA_Fdot_patch(int g_a, char t_a, int alo[], int ahi[], int g_b, char t_b,
 double NGA_Ddot_patch(int g_a, char t_a, int alo[], int ahi[], int g_b, char t_b, int blo[], int bhi[]);
 SingleComplex NGA_Cdot_patch(int g_a, char t_a, int alo[], int ahi[], int g_b, char t_b, int blo[], int bhi[]);
 DoubleComplex NGA_Zdot_patch(int g_a, char t_a, int alo[], int ahi[], int g_b, char t_b, int blo[], int bhi[]);
+/* Matrix multiply on the gfx950 matrix cores (capi.c GA_Dgemm, GA_Sgemm,
+   NGA_Matmul_patch -> global/src/matmul.c):
+     C = alpha * op(A) * op(B) + beta * C,   op(X) = X ('N' 'n') or its transpose ('T' 't')
+   on 2-D arrays of C_DBL or C_FLOAT, one type for all three; REGULAR or irregular block
+   maps, which need not agree.  Collective, GA_Sync on entry and exit.
+   Patch subscripts: alo/ahi, blo/bhi and clo/chi are C subscripts into the arrays AS
+   STORED, and op(A) is that stored patch or its transpose -- with m x k = op(A),
+   k x n = op(B), m x n = the C patch.  For 'N' this is the reference's meaning.  For 'T'
+   the reference's own range check (matmul.c:2105-2117) reads the same numbers as op()
+   coordinates and is inconsistent on non-square arrays; the rule here is the one above.
+   GA_Dgemm / GA_Sgemm are the patch form over the leading corners as stored: A's
+   m x k (k x m for 'T'), B's k x n (n x k for 'T'), C's m x n.
+   Owner computes: a rank cuts the C patch by its own block, fetches the rows of op(A)
+   and columns of op(B) it needs in panels of gaamd_ga_gemm_panel() values of k, counted
+   from the start of the patch's k range, into HBM scratch (freed before return) and runs
+   gaamd_gemm (ga_amd.h) into its block in place: the caller's beta on the first panel,
+   beta = 1 on the later ones.
+   Rank independence: with gaamd_gemm's order contract -- per element of C one sum from
+   +0 in increasing k within a panel, then alpha * sum + beta * C without FMA -- the
+   result for given arrays is the same bits on any number of ranks and any block maps,
+   as the dot products' is.  beta == 0 does not read C (a NaN there does not propagate).
+   Aborts through GA_Error, before the first sync or launch: a type that is not C_DBL /
+   C_FLOAT, differs between the arrays or does not match the call; a rank other than 2;
+   a trans other than N n T t; a patch out of range; patch extents that do not agree; an
+   array in a host segment; g_c equal to g_a or g_b with patches that overlap (an owner
+   would read what another rank is writing). */
+void GA_Dgemm(char ta, char tb, int m, int n, int k, double alpha, int g_a, int g_b, double beta, int g_c);
+void GA_Sgemm(char ta, char tb, int m, int n, int k, float alpha, int g_a, int g_b, float beta, int g_c);
+void NGA_Matmul_patch(char transa, char transb, void *alpha, void *beta, int g_a, int alo[], int ahi[],
+                      int g_b, int blo[], int bhi[], int g_c, int clo[], int chi[]);
+/* values of k per panel of the owner-computes loop (a fixed constant, 1024) */
+int gaamd_ga_gemm_panel(void);
 /* global arrays alive on this rank (temporaries of the general path are destroyed
    before their call returns) */
 int gaamd_ga_live_arrays(void);

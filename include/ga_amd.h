@@ -93,6 +93,40 @@ int gaamd_patch_dot  (int op, const void *a, const long long *a_stride, const vo
 int gaamd_patch_add_plan(int op, const void *a, const long long *a_stride, const void *b,
                          const long long *b_stride, const void *c, const long long *c_stride,
                          const long long *count, int ndim, long long plan[4]);
+/* Row-major GEMM on the gfx950 matrix cores, for op = COMEX_ACC_DBL (v_mfma_f64_16x16x4_f64)
+ * and COMEX_ACC_FLT (v_mfma_f32_16x16x4_f32); the kernel under GA_Dgemm / GA_Sgemm (ga.h):
+ *   C[i][j] = alpha * sum_k op(A)[i][k] * op(B)[k][j] + beta * C[i][j],  i < m, j < n, kk < k
+ * op(X) = X for trans 'N'/'n', its transpose for 'T'/'t'.  As stored, row-major with ld in
+ * ELEMENTS between rows: A is m x k ('N') or k x m ('T'), B is k x n or n x k, C is m x n.
+ * Any m, n, k >= 0, any ld >= the stored row length, bases aligned to the element; all
+ * offsets are 64-bit.  Nothing outside the m x n elements of C is written, nothing outside
+ * the stored elements of A and B is read.
+ * Summation order (a contract): every element of C has one accumulator, which starts at
+ * +0 and takes its k products in increasing k -- four consecutive k per matrix-core
+ * instruction, each instruction adding onto the result of the one before (for f32 this is
+ * bit for bit the fmaf chain over k; for f64 the instruction's own fixed order within its
+ * four).  The order does not depend on where the element lies in C or in the launch grid,
+ * nor on m and n: a sub-rectangle of C computed alone (offset base pointers, the same ld
+ * and k) has the bits it has in the whole product, and so has every repeat of a call.
+ * Then C = alpha * acc + beta * C as two products and one sum, no FMA (gaamd_patch_add's
+ * expression).  beta == 0: C is not read (a NaN there does not propagate) and
+ * C = alpha * acc.  alpha == 0 or k == 0: A and B are not read and C = beta * C
+ * (gaamd_patch_scale; all zeros when beta == 0 too).  m == 0 or n == 0: 0, no launch.
+ * Negative codes, nothing launched: -3 a negative extent, -4 an op other than DBL / FLT or
+ * a trans other than N n T t, -5 alpha or beta missing, -6 an ld below the stored row
+ * length, -7 2^31 tiles of C or more, -8 a base below element alignment, -11 C overlaps A
+ * or B.  Overlap is judged on byte spans, first stored element to last: C being exactly A
+ * overlaps, and so does a C that lies between the rows of B (inside B's ld padding, sharing
+ * no element with it); a C that begins where A's last element ends does not. */
+int gaamd_gemm(int op, int transa, int transb, long long m, long long n, long long k,
+               const void *alpha, const void *a, long long lda, const void *b, long long ldb,
+               const void *beta, void *c, long long ldc, void *stream);
+/* gaamd_gemm's checks without a launch (no GPU needed): 0 it would launch, 1 nothing to do
+ * (m or n is 0), or its error code; plan[0..5] = {tile M, tile N, tile K (the workgroup's
+ * tile of C and its k step), tiles along m = ceil(m / tile M), tiles along n, k steps} */
+int gaamd_gemm_plan(int op, int transa, int transb, long long m, long long n, long long k,
+                    const void *alpha, const void *a, long long lda, const void *b, long long ldb,
+                    const void *beta, const void *c, long long ldc, long long plan[6]);
 long gaamd_packed_size(const int *count, int stride_levels);
 int gaamd_pack(const void *src, const int *src_stride, const int *count, int stride_levels,
                void *packed, void *stream);
