@@ -215,6 +215,26 @@ def gemm_plan(op, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc):
     return rc, {"tm": out[0], "tn": out[1], "tk": out[2], "grid_m": out[3], "grid_n": out[4], "ksteps": out[5]}
 
 
+# row-major transpose through LDS tiles (gaamd_transpose): src, dst are device addresses,
+# ld in elements; the return code is handed back
+def transpose(op, rows, cols, src, lds, dst, ldd, stream=None):
+    return lib().gaamd_transpose(op, rows, cols, ctypes.c_void_p(src), lds, ctypes.c_void_p(dst), ldd, stream)
+
+
+# c = alpha * (c + b^T) in place (gaamd_transpose_acc): c is m x n, b is n x m; an alpha of
+# None reaches the library as NULL
+def transpose_acc(op, m, n, alpha, b, ldb, c, ldc, stream=None):
+    ka, ap = scale_buffer(op, alpha) if alpha is not None else (None, None)
+    return lib().gaamd_transpose_acc(op, m, n, ap, ctypes.c_void_p(b), ldb, ctypes.c_void_p(c), ldc, stream)
+
+
+def transpose_plan(op, rows, cols, src, lds, dst, ldd):
+    """gaamd_transpose's checks without a launch (no GPU): (code, {tile_rows, tile_cols, grid_rows, grid_cols})"""
+    out = (ctypes.c_longlong * 4)()
+    rc = lib().gaamd_transpose_plan(op, rows, cols, ctypes.c_void_p(src), lds, ctypes.c_void_p(dst), ldd, out)
+    return rc, {"tile_rows": out[0], "tile_cols": out[1], "grid_rows": out[2], "grid_cols": out[3]}
+
+
 def last_launch():
     k, w, u, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     b = ctypes.c_ulonglong()

@@ -281,6 +281,13 @@ SIGNATURES = {
                                        ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_longlong, c_ll_p]),
+    "gaamd_transpose": (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p,
+                                       ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]),
+    "gaamd_transpose_acc": (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong,
+                                           ctypes.c_void_p]),
+    "gaamd_transpose_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p,
+                                            ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, c_ll_p]),
     "gaamd_packed_size": (ctypes.c_long, [c_int_p, ctypes.c_int]),
     "gaamd_pack": (ctypes.c_int, [ctypes.c_void_p, c_int_p, c_int_p, ctypes.c_int, ctypes.c_void_p,
                                   ctypes.c_void_p]),
@@ -407,6 +414,9 @@ GA_SIGNATURES = {
     "NGA_Matmul_patch": (None, [ctypes.c_char, ctypes.c_char, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                 c_int_p, c_int_p, ctypes.c_int, c_int_p, c_int_p, ctypes.c_int, c_int_p, c_int_p]),
     "gaamd_ga_gemm_panel": (ctypes.c_int, []),
+    # transpose and symmetrize
+    "GA_Transpose": (None, [ctypes.c_int, ctypes.c_int]),
+    "GA_Symmetrize": (None, [ctypes.c_int]),
 }
 SIGNATURES.update(GA_SIGNATURES)
 

@@ -85,6 +85,7 @@ static struct {
     double acctot = 0, accloc = 0, scatot = 0, scaloc = 0, gattot = 0, gatloc = 0;
     // calls that compute on the arrays where they lie, and the bytes this rank's kernels moved
     long numfill = 0, numscale = 0, numadd = 0, numcopy = 0, numdot = 0, numgemm = 0;
+    long numtranspose = 0, numsymm = 0;
     double mathloc = 0;
 } g_stat;
 
@@ -1401,6 +1402,89 @@ void NGA_Matmul_patch(char transa, char transb, void *alpha, void *beta, int g_a
 }
 int gaamd_ga_gemm_panel(void) { return (int)kGemmPanel; }
 
+// ---- GA_Transpose / GA_Symmetrize ----------------------------------------------------
+// pnga_transpose (global.nalg.c:954) transposes a rank's block of A in a host buffer and
+// puts it into B; pnga_symmetrize (ga_symmetr.c:49) gets the mirror of a rank's block into
+// a host buffer and adds it there.  Here the destination's owner computes, as matmul_patch
+// does: a rank takes its own block of the destination -- rows r0..r1, columns c0..c1 as
+// stored -- gets the mirror patch of the source (rows c0..c1, columns r0..r1) into HBM
+// scratch of one block's size with NGA_Get's path, and runs the LDS-tiled kernel from the
+// scratch into its block in place.  The block maps of source and destination need not agree.
+
+// the mirror of this rank's part `s` of a 2-D array, fetched from g_src into new scratch:
+// stored count[0] x count[1] with ld = count[1]
+static void *get_mirror(int g_src, const GArray &dst, const Sub &s, const char *what) {
+    void *buf = gaamd_dev_malloc((size_t)s.count[0] * (size_t)s.count[1] * dst.elemsize);
+    if (!buf) fatal("%s: no device memory for the %lld x %lld scratch block", what, s.count[0], s.count[1]);
+    const long lo[2] = {s.plo[1], s.plo[0]}, hi[2] = {s.phi[1], s.phi[0]}, ld[1] = {(long)s.count[1]};
+    patch_op(GA_GET, g_src, lo, hi, buf, ld, nullptr);
+    return buf;
+}
+
+void GA_Transpose(int g_a, int g_b) {
+    const char *what = "GA_Transpose";
+    if (g_a == g_b) fatal("%s: the arrays have to be different", what);
+    GArray &a = arr(g_a), &b = arr(g_b);
+    if (a.ndim != 2 || b.ndim != 2) fatal("%s: arrays of rank other than 2 are not supported", what);
+    if (a.type != b.type) fatal("%s: types of the arrays differ", what);
+    if (a.dims[0] != b.dims[1] || a.dims[1] != b.dims[0])
+        fatal("%s: dims of the arrays do not agree: A is %ld x %ld, B is %ld x %ld", what, a.dims[1], a.dims[0],
+              b.dims[1], b.dims[0]);
+    need_hbm(a, what);
+    need_hbm(b, what);
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_stat.numtranspose++;
+    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
+    whole(b, lo, hi);
+    const Sub s = own_sub(b, lo, hi);
+    if (s.any) {
+        // the block is count[1] rows of count[0]; its mirror in A is count[0] rows of count[1].
+        // A mirror that lies wholly in this rank's own block of A is read there, without a get.
+        const long mlo[2] = {s.plo[1], s.plo[0]}, mhi[2] = {s.phi[1], s.phi[0]};
+        const Sub sa = own_sub(a, mlo, mhi);
+        const bool own = sa.any && sa.count[0] == s.count[1] && sa.count[1] == s.count[0];
+        void *buf = own ? nullptr : get_mirror(g_a, b, s, what);
+        const int rc = gaamd_transpose(b.optype, s.count[0], s.count[1], own ? sa.p : buf, own ? sa.ext[0] : s.count[1],
+                                       s.p, s.ext[0], gaamd_stream());
+        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        if (gaamd_sync(gaamd_stream()) != 0) fatal("%s: the stream failed", what);
+        if (buf) gaamd_dev_free(buf);
+        g_stat.mathloc += 2 * s.bytes;
+    }
+    math_end(what);
+}
+
+void GA_Symmetrize(int g_a) {
+    const char *what = "GA_Symmetrize";
+    GArray &a = arr(g_a);
+    if (a.ndim != 2) fatal("%s: arrays of rank other than 2 are not supported", what);
+    if (a.dims[0] != a.dims[1]) fatal("%s: the array is not square: %ld x %ld", what, a.dims[1], a.dims[0]);
+    if (a.type != C_DBL && a.type != C_FLOAT) fatal("%s: type %d is neither C_DBL nor C_FLOAT", what, a.type);
+    need_hbm(a, what);
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_stat.numsymm++;
+    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
+    whole(a, lo, hi);
+    const Sub s = own_sub(a, lo, hi);
+    // always through the scratch copy, on one rank too: in place, a block on the diagonal
+    // would read what it is writing
+    void *buf = s.any ? get_mirror(g_a, a, s, what) : nullptr;
+    if (gaamd_sync(gaamd_stream()) != 0) fatal("%s: the stream failed", what);
+    comex_barrier(COMEX_GROUP_WORLD);   // every rank has read before any rank writes (ga_symmetr.c:105)
+    if (s.any) {
+        const double half_d = 0.5;
+        const float half_f = 0.5f;
+        const void *half = a.type == C_DBL ? (const void *)&half_d : (const void *)&half_f;
+        const int rc = gaamd_transpose_acc(a.optype, s.count[1], s.count[0], half, buf, s.count[1], s.p, s.ext[0],
+                                           gaamd_stream());
+        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        if (gaamd_sync(gaamd_stream()) != 0) fatal("%s: the stream failed", what);
+        gaamd_dev_free(buf);
+        g_stat.mathloc += 3 * s.bytes;
+    }
+    math_end(what);
+}
+
 void GA_Print_stats(void) {
     printf("[%d] GA on-device calls: fill %ld, scale %ld, add %ld, copy %ld, dot %ld; local bytes moved %.0f; "
            "gemm %ld\n",
@@ -1410,6 +1494,7 @@ void GA_Print_stats(void) {
            my_rank(), g_stat.numacc, g_stat.numput, g_stat.numget, g_stat.numsca, g_stat.numgat);
     printf("[%d] accumulate bytes total %.0f, local %.0f (%.1f%%)\n", my_rank(), g_stat.acctot, g_stat.accloc,
            g_stat.acctot > 0 ? 100.0 * g_stat.accloc / g_stat.acctot : 0.0);
+    printf("[%d] GA transposes: transpose %ld, symmetrize %ld\n", my_rank(), g_stat.numtranspose, g_stat.numsymm);
 }
 
 }  // extern "C"

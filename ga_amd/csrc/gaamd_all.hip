@@ -9,3 +9,4 @@
 #include "gaamd_misc.hip"
 #include "gaamd_patch.hip"
 #include "gaamd_gemm.hip"
+#include "gaamd_transpose.hip"

@@ -156,6 +156,19 @@ int plan_gemm(int op, int transa, int transb, long long m, long long n, long lon
               const void *a, long long lda, const void *b, long long ldb, const void *beta, const void *c,
               long long ldc, long long plan[6]);
 
+// ---- row-major transpose through LDS (gaamd_transpose.hip; ga_amd.h gaamd_transpose) ----
+// op: any COMEX_ACC_* type (transpose, for the element size) or DBL / FLT (transpose_acc);
+// ld in elements; the codes are the patch codes above, with gaamd_gemm's meanings.
+constexpr int kTransposeTile = 64, kTransposeTile16 = 32;   // tile side for 4- / 8-byte and for 16-byte elements
+int launch_transpose(int op, long long rows, long long cols, const void *src, long long lds, void *dst, long long ldd,
+                     hipStream_t stream);
+int launch_transpose_acc(int op, long long m, long long n, const void *alpha, const void *b, long long ldb, void *c,
+                         long long ldc, hipStream_t stream);
+// launch_transpose's checks without a launch (no device): 0 launch, 1 nothing to do, < 0 error;
+// plan[0..3] = {tile rows, tile cols, tiles along rows, tiles along cols}
+int plan_transpose(int op, long long rows, long long cols, const void *src, long long lds, const void *dst,
+                   long long ldd, long long plan[4]);
+
 // comex_rmw: fetch-and-add (swap == 0) or swap of one 4- or 8-byte word at
 // `addr` (device-accessible); the old value lands in *out_dev (8 bytes)
 int launch_rmw(int swap, void *addr, int bytes, uint64_t val, uint64_t *out_dev, hipStream_t stream);

@@ -113,6 +113,21 @@ int gaamd_gemm_plan(int op, int transa, int transb, long long m, long long n, lo
     return plan_gemm(op, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, plan);
 }
 
+int gaamd_transpose(int op, long long rows, long long cols, const void *src, long long lds, void *dst, long long ldd,
+                    void *stream) {
+    return launch_transpose(op, rows, cols, src, lds, dst, ldd, stream_of(stream));
+}
+
+int gaamd_transpose_acc(int op, long long m, long long n, const void *alpha, const void *b, long long ldb, void *c,
+                        long long ldc, void *stream) {
+    return launch_transpose_acc(op, m, n, alpha, b, ldb, c, ldc, stream_of(stream));
+}
+
+int gaamd_transpose_plan(int op, long long rows, long long cols, const void *src, long long lds, const void *dst,
+                         long long ldd, long long plan[4]) {
+    return plan_transpose(op, rows, cols, src, lds, dst, ldd, plan);
+}
+
 long gaamd_packed_size(const int *count, int stride_levels) {
     long n = count[0];
     for (int j = 1; j <= stride_levels; ++j) n *= count[j];

@@ -151,6 +151,28 @@ void NGA_Matmul_patch(char transa, char transb, void *alpha, void *beta, int g_a
                       int g_b, int blo[], int bhi[], int g_c, int clo[], int chi[]);
 /* values of k per panel of the owner-computes loop (a fixed constant, 1024) */
 int gaamd_ga_gemm_panel(void);
+/* Transpose and symmetrize on HBM blocks (capi.c GA_Transpose -> pnga_transpose,
+   global.nalg.c:954; GA_Symmetrize -> pnga_symmetrize, ga_symmetr.c:49):
+     GA_Transpose:   B = A^T          2-D arrays of one type, any of the six; B's dims are
+                                      A's reversed; a bit copy (NaN payloads, -0 survive)
+     GA_Symmetrize:  A = 0.5*(A+A^T)  a square 2-D array of C_DBL or C_FLOAT
+   REGULAR or irregular block maps, which need not agree between A and B.  Collective,
+   GA_Sync on entry and exit.
+   Destination owner computes: a rank takes its own block of the destination (rows
+   r0..r1, columns c0..c1 as stored), gets the mirror patch of the source (rows c0..c1,
+   columns r0..r1) into HBM scratch of one block's size with NGA_Get's path, and runs
+   gaamd_transpose / gaamd_transpose_acc (ga_amd.h) from the scratch into its block in
+   place; the scratch is freed before return.  GA_Symmetrize always goes through the
+   scratch copy, and holds a barrier between the gets and the kernels: every rank has read
+   before any rank writes.  Each element is 0.5 * (a_ij + a_ji), one add and one multiply,
+   so the result equals its own transpose bit for bit and is the same bits on any number of
+   ranks and any block map.
+   Aborts through GA_Error, before the first sync or launch: g_a == g_b, a rank other
+   than 2, types that differ, B's dims not A's reversed (transpose); a rank other than 2,
+   an array that is not square, a type other than C_DBL / C_FLOAT (symmetrize); an array
+   in a host segment (both). */
+void GA_Transpose(int g_a, int g_b);
+void GA_Symmetrize(int g_a);
 /* global arrays alive on this rank (temporaries of the general path are destroyed
    before their call returns) */
 int gaamd_ga_live_arrays(void);

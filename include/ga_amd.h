@@ -127,6 +127,34 @@ int gaamd_gemm(int op, int transa, int transb, long long m, long long n, long lo
 int gaamd_gemm_plan(int op, int transa, int transb, long long m, long long n, long long k,
                     const void *alpha, const void *a, long long lda, const void *b, long long ldb,
                     const void *beta, const void *c, long long ldc, long long plan[6]);
+/* Row-major transpose through LDS tiles; the kernels under GA_Transpose / GA_Symmetrize (ga.h).
+ *   gaamd_transpose:      dst[j][i] = src[i][j],  i < rows, j < cols
+ *     src is rows x cols, dst is cols x rows.  A pure bit copy: op is any COMEX_ACC_* code and
+ *     only gives the element size (INT FLT 4, DBL CPL LNG 8, DCP 16 bytes); NaN payloads and
+ *     -0 survive.
+ *   gaamd_transpose_acc:  c[i][j] = alpha * (c[i][j] + b[j][i]),  i < m, j < n
+ *     c is m x n, in place; b is n x m.  op = COMEX_ACC_DBL or COMEX_ACC_FLT.  The reference's
+ *     expression (ga_symmetr.c:41): one add, then one multiply -- not alpha*c + alpha*b, no FMA.
+ * Row-major with ld in ELEMENTS between rows; any extents >= 0, any ld >= the stored row
+ * length, bases aligned to the element; all offsets are 64-bit.  A side whose base and ld are
+ * multiples of 16 bytes moves 16-byte vectors, any other side single elements (decided per
+ * launch).  Nothing outside the source's elements is read, nothing outside the destination's
+ * elements -- its ld padding included -- is written.  A zero extent: 0, no launch.
+ * Negative codes, nothing launched, with gaamd_gemm's meanings: -3 a negative extent, -4 an
+ * unknown op (for _acc: anything but DBL / FLT), -5 alpha missing, -6 an ld below the stored
+ * row length, -7 2^31 tiles or more, -8 a base below element alignment, -11 the byte spans of
+ * source and destination (first stored element to last) overlap: dst equal to src overlaps,
+ * and so does a dst inside src's ld padding; a dst that begins where src's last element ends
+ * does not. */
+int gaamd_transpose(int op, long long rows, long long cols,
+                    const void *src, long long lds, void *dst, long long ldd, void *stream);
+int gaamd_transpose_acc(int op, long long m, long long n, const void *alpha,
+                        const void *b, long long ldb, void *c, long long ldc, void *stream);
+/* gaamd_transpose's checks without a launch (no GPU needed): 0 it would launch, 1 nothing to
+ * do (rows or cols is 0), or its error code; plan[0..3] = {tile rows, tile cols (of src, in
+ * elements), tiles along rows = ceil(rows / tile rows), tiles along cols} */
+int gaamd_transpose_plan(int op, long long rows, long long cols, const void *src,
+                         long long lds, const void *dst, long long ldd, long long plan[4]);
 long gaamd_packed_size(const int *count, int stride_levels);
 int gaamd_pack(const void *src, const int *src_stride, const int *count, int stride_levels,
                void *packed, void *stream);
