@@ -117,7 +117,7 @@ __global__ __launch_bounds__(64) void k_iov_serial(const IovDesc d, const OP op)
     }
 }
 
-constexpr uint32_t kIovRunSkip = 0xffffffffu;   // k_iov_runs: a run of this key was applied already
+// kIovRunSkip (gaamd_kernels.h): k_iov_runs skips a run of this key, it was applied already
 
 // the hashed path's state for one launch (see k_iovh_insert below)
 struct IovHashArgs {
@@ -1058,7 +1058,7 @@ int launch_iov_runs(int op, const void *scale, IovDesc d, uint64_t align_or, uin
     const int esz = elem_size(op);
     if (!esz || d.bytes <= 0 || d.bytes > kIovRunsMaxBytes || !d.dst_list) return -4;
     if (op != kOpCopy && !scale) return -5;
-    if (units > (1ull << 32)) return -7;
+    if (!iov_units_ok(units)) return -7;
     const int64_t row = (op == kOpCopy) ? d.bytes : (int64_t)(d.bytes / esz) * esz;   // acc.h:122
     if (d.n == 0 || row == 0) return 0;
     if (work_bytes < iov_runs_work_bytes(d.n)) return -6;
@@ -1082,7 +1082,7 @@ int launch_iov_runs(int op, const void *scale, IovDesc d, uint64_t align_or, uin
     while (end_bit < 32 && (1ull << end_bit) < units) ++end_bit;
     if (mask) {
         // the pairs the hashed launch applied already sort last (sentinel key)
-        if (mask->n != d.n || mask->dlo != dlo || units >= (uint64_t)kIovRunSkip) return -9;
+        if (mask->n != d.n || mask->dlo != dlo) return -9;
         const uint64_t P = mask->P;
         const uint32_t *dup = (const uint32_t *)(mask->mem + P * 8);
         const uint32_t *slot = (const uint32_t *)(mask->mem + iovh_off_slot((uint32_t)P));
@@ -1092,7 +1092,7 @@ int launch_iov_runs(int op, const void *scale, IovDesc d, uint64_t align_or, uin
     } else if (pmask) {
         // the pairs of partitions k_iov_part applied sort last (sentinel key); then the
         // deferred partitions' counters back to zero
-        if (!pmask->counts || units >= (uint64_t)kIovRunSkip) return -9;
+        if (!pmask->counts) return -9;
         hipLaunchKernelGGL(k_iov_keys_partmask, dim3((d.n + 255u) / 256u), dim3(256), 0, stream, d.dst_list, dlo,
                            (uint32_t)d.bytes, d.n, pmask->counts, pmask->lg, kin, vin);
         hipError_t e0 = hipGetLastError();
@@ -1121,7 +1121,8 @@ int launch_iov_hashed(IovHash *h, int op, const void *scale, IovDesc d, uint64_t
     const int esz = elem_size(op);
     if (!esz || d.bytes <= 0 || d.bytes > kIovRunsMaxBytes || !d.dst_list) return -4;
     if (op != kOpCopy && !scale) return -5;
-    if (d.n > kIovhMaxPairs || units >= (uint64_t)kIovRunSkip) return 1;   // the radix path
+    if (!iov_units_ok(units)) return -7;
+    if (d.n > kIovhMaxPairs) return 1;   // the radix path
     const int64_t row = (op == kOpCopy) ? d.bytes : (int64_t)(d.bytes / esz) * esz;   // acc.h:122
     if (d.n == 0 || row == 0) return 0;
     uint64_t a = align_or | (uint64_t)row | 16;
@@ -1194,7 +1195,7 @@ int launch_iov_lds(int op, const void *scale, IovDesc d, uint64_t align_or, uint
     const int esz = elem_size(op);
     if (!esz || d.bytes <= 0 || d.bytes > kIovRunsMaxBytes || !d.dst_list) return -4;
     if (op != kOpCopy && !scale) return -5;
-    if (units > (1ull << 32)) return 1;   // another path
+    if (!iov_units_ok(units)) return -7;
     const int64_t row = (op == kOpCopy) ? d.bytes : (int64_t)(d.bytes / esz) * esz;   // acc.h:122
     if (d.n == 0 || row == 0) return 0;
     uint64_t a = align_or | (uint64_t)row | 16;

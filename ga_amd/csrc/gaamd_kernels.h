@@ -222,9 +222,20 @@ int launch_iov(int op, const void *scale, IovDesc d, uint64_t align_or, bool ser
 // the GPU (stable radix sort of (dst - dlo) / bytes, so equal destinations keep
 // their input order) and one lane per distinct destination applies its pairs in
 // input order -- the reference's pair order wherever it matters.  Requires a
-// device dst list, every dst - dlo a multiple of d.bytes, (dhi - dlo) / bytes
-// < 2^32, d.bytes <= kIovRunsMaxBytes, and no source inside a destination.
+// device dst list, every dst - dlo a multiple of d.bytes, iov_units_ok(units),
+// d.bytes <= kIovRunsMaxBytes, and no source inside a destination.
 constexpr int kIovRunsMaxBytes = 256;
+// `units` of every GPU-ordered launcher: the slots of d.bytes from dlo up to the end of
+// the highest destination, so the 32-bit sort keys (dst - dlo) / bytes are 0 .. units - 1.
+// The key 0xffffffff is kIovRunSkip, the mark of the masked passes for "this pair was
+// applied already", and k_iov_runs skips it on every route: units < kIovRunSkip is the
+// one limit, the same for the classification (iov.cpp, the requester and the owner in
+// remote.cpp) and for launch_iov_runs / _hashed / _lds, masked or not.  From 0xffffffff
+// units up the callers take the host-checked plain or serial kernel.
+constexpr uint32_t kIovRunSkip = 0xffffffffu;
+// dend: one past the last byte of the highest destination
+inline uint64_t iov_units(uint64_t dlo, uint64_t dend, int bytes) { return (dend - dlo) / (uint64_t)bytes; }
+inline bool iov_units_ok(uint64_t units) { return units < (uint64_t)kIovRunSkip; }
 size_t iov_runs_work_bytes(uint32_t n);
 struct IovPartState;   // the partitioned path's deferred overflow (below)
 struct IovHash;   // the hashed path's table (one per calling thread; kept across calls)

@@ -498,12 +498,11 @@ static bool iov_local(int cop, const void *scale, const uint64_t *src, const uin
                                                : off % (uint64_t)bytes == 0;
             }
         }
-        const uint64_t units = (dhi - dlo) / (uint64_t)bytes + 1;
         if (cross) {
             serial = true;
         } else if (dst_seq) {
             // one contiguous vector of destinations in pair order: none repeats or overlaps
-        } else if (congruent && bytes <= kIovRunsMaxBytes && units <= (1ull << 32)) {
+        } else if (congruent && bytes <= kIovRunsMaxBytes && iov_units_ok(iov_units(dlo, dhi, bytes))) {
             // destinations on a grid of whole pairs overlap only by repeating: from
             // kIovRunsMin pairs, or when a host hash check finds a repeat among fewer, the
             // GPU orders them (before, a small scatter with one repeated destination went
@@ -562,7 +561,7 @@ static bool iov_local(int cop, const void *scale, const uint64_t *src, const uin
     } else if (up_hi > up_lo) {
         upload_pinned(dev + up_lo, up + up_lo, up_hi - up_lo, r.streams[si]);
     }
-    const uint64_t units = runs ? (dhi - dlo) / (uint64_t)bytes + 1 : 0;
+    const uint64_t units = runs ? iov_units(dlo, dhi, bytes) : 0;
     int rc;
     if (runs) {
         // repeated destinations: the hashed path (sorts only the pairs that share a
@@ -903,7 +902,7 @@ int xfer_vec(Xfer kind, int op, void *scale, comex_giov_t *darr, int len, int pr
             // repeated destinations: the owner orders them on its GPU when every destination
             // is a whole number of pairs from dlo, else a host check picks the serial kernel
             int mode = 0;
-            bool congruent = bytes <= kIovRunsMaxBytes && (dhi - dlo) / (uint64_t)bytes < (1ull << 32);
+            bool congruent = bytes <= kIovRunsMaxBytes && iov_units_ok(iov_units(dlo, dhi, bytes));
             for (int i = 0; i < m && congruent; ++i) congruent = (dv[(size_t)i0 + i] - dlo) % (uint64_t)bytes == 0;
             if (congruent) {
                 // the owner orders repeats on its GPU; fewer pairs with none go plain

@@ -311,7 +311,7 @@ static void progress_loop() {
                 d.bytes = q.count[0];
                 d.n = (uint32_t)q.count[1];
                 int rc = 1;
-                const uint64_t units = (q.dst_hi - q.dst_addr) / (uint64_t)d.bytes + 1;
+                const uint64_t units = iov_units(q.dst_addr, q.dst_hi, d.bytes);
                 if (q.iov_serial == 2 && d.n < kIovLdsRoute && tuning().iov_lds)
                     // below 1 Ki pairs: ordered and applied by one workgroup, in LDS
                     rc = launch_iov_lds(q.op, q.scale, d, q.iov_align, q.dst_addr, units, r.streams[si]);

@@ -143,3 +143,25 @@ def test_add_rejects_partial_overlap():
     # the entry point itself returns the code, before any launch
     assert ga_amd.patch_add(DBL, 1.0, BASE + 8, [], 1.0, far, [], BASE, [], [100]) == E_OVERLAP
     assert ga_amd.patch_add(DBL, 1.0, BASE, [96], 1.0, far, [80], BASE, [80], [7, 5]) == E_OVERLAP
+
+
+@pytest.mark.parametrize("op", [DBL, FLT, DCP])
+def test_far_strides_plan_like_compact_ones(op):
+    """the strides of tests/test_gpu_far_offsets.py (rows 2 GiB + 48 apart) on a, b and c
+    in turn: accepted, with the vector width, levels, rows and vectors a row of the same
+    counts at compact strides (where those do not merge levels)"""
+    from test_gpu_far_offsets import PATCH_SHAPES
+    es = ga_amd.OP_DTYPE[op].itemsize
+    far1, far2 = BASE + (1 << 36), BASE + (2 << 36)
+    for count, stride in PATCH_SHAPES:
+        for off in ((0, 4) if op == FLT else (0,)):
+            # compact, with padding after every row and plane so that no levels merge
+            pad = [(count[0] + 4) * es]
+            for c in count[1:-1]:
+                pad.append(pad[-1] * (c + 1))
+            rc, compact = ga_amd.patch_add_plan(op, far1 + off, pad, far2 + off, pad, BASE + off, pad, count)
+            assert rc == 0 and compact["levels"] == len(count) - 1, compact
+            for which in range(3):
+                st = [stride if w == which else pad for w in range(3)]
+                rc, p = ga_amd.patch_add_plan(op, far1 + off, st[0], far2 + off, st[1], BASE + off, st[2], count)
+                assert rc == 0 and p == compact, (count, which, p, compact)

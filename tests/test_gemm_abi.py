@@ -142,3 +142,27 @@ def test_overlap_is_judged_on_byte_spans():
     # A and B are only read
     assert both(DBL, "N", "N", m, n, k, 8, 8, 8, a=A, b=A) == 0
     assert both(FLT, "N", "N", m, n, k, 8, 8, 8, a=A, b=A + 4) == 0
+
+
+@pytest.mark.parametrize("op", [DBL, FLT])
+@pytest.mark.parametrize("vec", [False, True], ids=["odd", "vec"])
+def test_far_leading_dimensions_plan_like_compact_ones(op, vec):
+    """the leading dimensions of tests/test_gpu_far_offsets.py (an operand's rows spread
+    over 9 GiB) on each operand in turn: accepted, with the tiles and the grid of compact
+    ones; the operands are 64 GiB apart, so no span meets another"""
+    from test_gpu_far_offsets import far_ld, stored_shape
+    es = 8 if op == DBL else 4
+    rc, p0 = ga_amd.gemm_plan(op, "N", "N", 1, 1, 1, 1.0, A, 1, B, 1, 1.0, C, 1)
+    m, n, k = p0["tm"] + 1, p0["tn"] + 1, p0["tk"] + 1
+    for ta in "NT":
+        for tb in "NT":
+            ld = {w: stored_shape(w, ta, tb, m, n, k)[1] + 5 for w in "ABC"}
+            rc, compact = ga_amd.gemm_plan(op, ta, tb, m, n, k, 2.0, A, ld["A"], B, ld["B"], -3.0, C, ld["C"])
+            assert rc == 0 and (compact["grid_m"], compact["grid_n"], compact["ksteps"]) == (2, 2, 2)
+            for which in "ABC":
+                rows = stored_shape(which, ta, tb, m, n, k)[0]
+                big = dict(ld)
+                big[which] = far_ld(rows, es, vec)
+                assert (rows - 1) * big[which] * es >= 9 << 30 and (big[which] * es % 16 == 0) == vec
+                rc, p = ga_amd.gemm_plan(op, ta, tb, m, n, k, 2.0, A, big["A"], B, big["B"], -3.0, C, big["C"])
+                assert rc == 0 and p == compact, (ta, tb, which, p, compact)

@@ -26,9 +26,9 @@ log-uniformly to 150 000, which almost never lands on one of them.  Here
     back at zero, or the second result differs).
 
 No tolerance anywhere; NaNs match any NaN (helpers.same_bits_nan_aware).
-Read, not tested here: launch_iov_lds accepts `units` up to 2^32 where the deferred
-launch_iov_runs rejects units >= 0xffffffff; reaching that needs a destination span of
-16 GiB or more.
+Destination spans of 8 to 16 GiB and the limit on `units` (every GPU-ordered route takes
+units < 0xffffffff, the classification and the launchers alike; from there up the
+host-checked kernels): tests/test_gpu_far_offsets.py.
 """
 import ctypes
 import os

@@ -19,8 +19,8 @@ cols each run over {1, T-1, T, T+1, 2T+3}.
   position   a sub-rectangle transposed alone (offset bases, the same ld) has the bits it
              has in the whole
 
-Not tested: spans past 4 GiB, where the 64-bit offsets matter; that arithmetic is read,
-not run (a test of it would need buffers of that size).
+Spans past 2 GiB and 4 GiB, where the 64-bit offsets matter (rows spread over 9 GiB, only
+the rows touched): tests/test_gpu_far_offsets.py.
 """
 import numpy as np
 import pytest

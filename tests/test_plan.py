@@ -215,3 +215,34 @@ def test_rows_off_lines_on_both_sides_take_the_rows_kernel():
         assert plan(DBL, SRC, [4064], DST, [4064], [2032, 1000], 1)["kind"] == "flat"
     finally:
         ga_amd.set_tuning("flat_line_min", old)
+
+
+@pytest.mark.parametrize("kind", [0, 1, 2])
+def test_far_strides_plan_like_compact_ones(kind):
+    """the strides of tests/test_gpu_far_offsets.py (levels of 1 GiB + 64 and 2 GiB - 16) on
+    dst, then on src: the kernel family, vector width, unroll, block and blocks of the same
+    counts at padded compact strides, by the launcher's choice and with the kind knob"""
+    from test_gpu_far_offsets import COLRED_ROW, G, strided_geos
+    old = ga_amd.set_tuning("kind", kind)
+    try:
+        for geo, strides, counts in strided_geos():
+            off = geo.base % 16
+            count = [geo.row] + list(counts)
+            pad = [geo.row + 64]
+            for c in counts[:-1]:
+                pad.append(pad[-1] * (c + 1))
+            for op in (37, DBL, DCP, COPY):
+                compact = plan(op, SRC + off, pad, DST + off, pad, count, len(counts))
+                want = {"auto": "flat" if geo.row < 1024 else "rows"}.get(ga_amd.KIND_NAME[kind], ga_amd.KIND_NAME[kind])
+                assert compact["kind"] == want, (geo.name, compact)
+                for ss, ds in ((pad, strides), (strides, pad)):
+                    p = plan(op, SRC + off, ss, DST + off, ds, count, len(counts))
+                    assert p == compact, (geo.name, op, p, compact)
+    finally:
+        ga_amd.set_tuning("kind", old)
+    if kind == 0:
+        # the column reductions: far source rows into one destination row
+        for op in (42, DBL):
+            near = plan(op, SRC, [COLRED_ROW + 64], DST, [0], [COLRED_ROW, 5], 1)
+            p = plan(op, SRC, [G + 64], DST, [0], [COLRED_ROW, 5], 1)
+            assert p["kind"] == "ordered" and p == near, (p, near)

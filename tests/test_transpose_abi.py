@@ -146,3 +146,21 @@ def test_overlap_is_judged_on_byte_spans():
     # the same rule for the accumulating form: c is the destination
     assert ga_amd.transpose_acc(DBL, rows, rows, 0.5, SRC, 8, SRC, 8) == E_OVERLAP
     assert ga_amd.transpose_acc(FLT, 3, 4, 0.5, SRC, 16, SRC + 8 * 4, 16) == E_OVERLAP
+
+
+@pytest.mark.parametrize("op", [INT, DBL, DCP, FLT])
+@pytest.mark.parametrize("vec", [False, True], ids=["odd", "vec"])
+def test_far_leading_dimensions_plan_like_compact_ones(op, vec):
+    """the leading dimensions of tests/test_gpu_far_offsets.py (T + 1 rows spread over
+    9 GiB) on src, then on dst: accepted, with the tiles and the grid of compact ones (the
+    plan reports no more than these); the accumulating form takes them up to its launch"""
+    from test_gpu_far_offsets import compact_ld, far_ld
+    rc, p0 = ga_amd.transpose_plan(op, 1, 1, SRC, 1, DST, 1)
+    t = p0["tile_rows"] + 1
+    small, big = compact_ld(t, ESZ[op], vec), far_ld(t, ESZ[op], vec)
+    assert (t - 1) * big * ESZ[op] >= 9 << 30 and (big * ESZ[op] % 16 == 0) == (vec or ESZ[op] == 16)
+    rc, compact = ga_amd.transpose_plan(op, t, t, SRC, small, DST, small)
+    assert rc == 0 and (compact["grid_rows"], compact["grid_cols"]) == (2, 2)
+    for lds, ldd in ((big, small), (small, big)):
+        rc, p = ga_amd.transpose_plan(op, t, t, SRC, lds, DST, ldd)
+        assert rc == 0 and p == compact, (lds, ldd, p, compact)
