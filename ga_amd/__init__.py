@@ -183,6 +183,40 @@ def patch_dot(op, a, a_stride, b, b_stride, count, stream=None):
     return rc, out
 
 
+# element-wise algebra (gaamd_patch_elem1 / _elem2): fn is one of these; the return code is
+# handed back (0, GAAMD_ZERO_DIVISOR, or the negative codes of ga_amd.h)
+GAAMD_ELEM_ABS, GAAMD_ELEM_ADD_CONST, GAAMD_ELEM_RECIP = 1, 2, 3
+GAAMD_ELEM_MUL, GAAMD_ELEM_DIV, GAAMD_ELEM_MAX, GAAMD_ELEM_MIN = 4, 5, 6, 7
+GAAMD_ZERO_DIVISOR = 2
+
+
+def patch_elem1(op, fn, dst, dst_stride, count, scalar=None, stream=None):
+    """dst = fn(dst) in place; scalar (ADD_CONST): one element, None reaches the library as NULL"""
+    keep, sp = scale_buffer(op, scalar) if scalar is not None else (None, None)
+    return lib().gaamd_patch_elem1(op, fn, sp, ctypes.c_void_p(dst), ll_array(dst_stride), ll_array(count),
+                                   len(count), stream)
+
+
+def patch_elem2(op, fn, a, a_stride, b, b_stride, c, c_stride, count, stream=None):
+    """c = fn(a, b)"""
+    return lib().gaamd_patch_elem2(op, fn, ctypes.c_void_p(a), ll_array(a_stride), ctypes.c_void_p(b),
+                                   ll_array(b_stride), ctypes.c_void_p(c), ll_array(c_stride), ll_array(count),
+                                   len(count), stream)
+
+
+def patch_select(op, want_max, a, a_stride, count, stream=None):
+    """(return code, the element as a one-element numpy array of the op's type, its key as a
+    one-element array -- the element's own type, complex: its real type --, its linear index)"""
+    dt = OP_DTYPE[op]
+    val = np.zeros(1, dtype=dt)
+    key = np.zeros(1, dtype=val.real.dtype)
+    idx = ctypes.c_longlong(-2)
+    rc = lib().gaamd_patch_select(op, int(bool(want_max)), ctypes.c_void_p(a), ll_array(a_stride), ll_array(count),
+                                  len(count), val.ctypes.data_as(ctypes.c_void_p),
+                                  key.ctypes.data_as(ctypes.c_void_p), ctypes.byref(idx), stream)
+    return rc, val, key, idx.value
+
+
 def patch_add_plan(op, a, a_stride, b, b_stride, c, c_stride, count):
     """gaamd_patch_add's checks without a launch (no GPU): (code, {width, levels, rows, nvec})"""
     out = (ctypes.c_longlong * 4)()

@@ -273,6 +273,12 @@ SIGNATURES = {
                                        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "gaamd_patch_add_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, c_ll_p, ctypes.c_void_p, c_ll_p,
                                             ctypes.c_void_p, c_ll_p, c_ll_p, ctypes.c_int, c_ll_p]),
+    "gaamd_patch_elem1": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, c_ll_p, c_ll_p,
+                                         ctypes.c_int, ctypes.c_void_p]),
+    "gaamd_patch_elem2": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_ll_p, ctypes.c_void_p,
+                                         c_ll_p, ctypes.c_void_p, c_ll_p, c_ll_p, ctypes.c_int, ctypes.c_void_p]),
+    "gaamd_patch_select": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_ll_p, c_ll_p, ctypes.c_int,
+                                          ctypes.c_void_p, ctypes.c_void_p, c_ll_p, ctypes.c_void_p]),
     "gaamd_gemm": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong,
                                   ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
                                   ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
@@ -417,6 +423,18 @@ GA_SIGNATURES = {
     # transpose and symmetrize
     "GA_Transpose": (None, [ctypes.c_int, ctypes.c_int]),
     "GA_Symmetrize": (None, [ctypes.c_int]),
+    # element-wise algebra and element selection
+    "GA_Abs_value": (None, [ctypes.c_int]),
+    "GA_Abs_value_patch": (None, [ctypes.c_int, c_int_p, c_int_p]),
+    "GA_Add_constant": (None, [ctypes.c_int, ctypes.c_void_p]),
+    "GA_Add_constant_patch": (None, [ctypes.c_int, c_int_p, c_int_p, ctypes.c_void_p]),
+    "GA_Recip": (None, [ctypes.c_int]),
+    "GA_Recip_patch": (None, [ctypes.c_int, c_int_p, c_int_p]),
+    **{f"GA_Elem_{n}": (None, [ctypes.c_int, ctypes.c_int, ctypes.c_int])
+       for n in ("multiply", "divide", "maximum", "minimum")},
+    **{f"GA_Elem_{n}_patch": (None, [ctypes.c_int, c_int_p, c_int_p, ctypes.c_int, c_int_p, c_int_p, ctypes.c_int,
+                                     c_int_p, c_int_p]) for n in ("multiply", "divide", "maximum", "minimum")},
+    "NGA_Select_elem": (None, [ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, c_int_p]),
 }
 SIGNATURES.update(GA_SIGNATURES)
 

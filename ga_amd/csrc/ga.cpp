@@ -30,6 +30,8 @@
 #include "../../include/comex.h"
 #include "../../include/ga_amd.h"
 #pragma GCC visibility pop
+#include <limits.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -86,6 +88,8 @@ static struct {
     // calls that compute on the arrays where they lie, and the bytes this rank's kernels moved
     long numfill = 0, numscale = 0, numadd = 0, numcopy = 0, numdot = 0, numgemm = 0;
     long numtranspose = 0, numsymm = 0;
+    long numelem[8] = {0};   // by GAAMD_ELEM_* code
+    long numselect = 0;
     double mathloc = 0;
 } g_stat;
 
@@ -1280,6 +1284,210 @@ GAAMD_DOT(SingleComplex, Cdot, C_SCPL)
 GAAMD_DOT(DoubleComplex, Zdot, C_DCPL)
 #undef GAAMD_DOT
 
+// ---- element-wise algebra and NGA_Select_elem ------------------------------------------
+// pnga_abs_value ... pnga_elem_minimum_patch (global/src/elem_alg.c) loop over the local
+// block on the host; here each rank runs gaamd_patch_elem1 / _elem2 on its part in HBM.
+
+// RECIP / DIV: after the kernel has completed and math_end's barrier, the ranks combine
+// their zero-divisor flags; if any is set every rank ends here, none waits in a barrier
+static void zero_divisor_end(int flag, const char *what) {
+    char mx[] = "max";
+    armci_msg_igop(&flag, 1, mx);
+    if (flag)
+        fatal("%s: zero divisor (the reference aborts at the first one; here those elements were left unwritten)",
+              what);
+}
+
+static void elem1_patch(int fn, int g_a, const long *lo, const long *hi, const void *alpha, const char *what) {
+    GArray &a = arr(g_a);
+    need_hbm(a, what);
+    check_patch(a, lo, hi, what);
+    if (fn == GAAMD_ELEM_ADD_CONST && !alpha) fatal("%s: alpha is missing", what);
+    comex_barrier(COMEX_GROUP_WORLD);   // fences every pending one-sided operation, then syncs
+    const Sub s = own_sub(a, lo, hi);
+    g_stat.numelem[fn]++;
+    int zero = 0;
+    if (s.any) {
+        const int rc = gaamd_patch_elem1(a.optype, fn, alpha, s.p, s.stride, s.count, a.ndim, gaamd_stream());
+        if (rc == GAAMD_ZERO_DIVISOR) zero = 1;
+        else if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        g_stat.mathloc += 2 * s.bytes;
+    }
+    math_end(what);
+    if (fn == GAAMD_ELEM_RECIP) zero_divisor_end(zero, what);
+}
+
+// ngai_elem2_patch_ (elem_alg.c:1851-1990): add_patch's structure, temporaries included
+static void elem2_patch(int fn, int g_a, const long *alo, const long *ahi, int g_b, const long *blo, const long *bhi,
+                        int g_c, const long *clo, const long *chi, const char *what) {
+    int tmp[2] = {0, 0}, use[2] = {g_a, g_b};
+    {
+        GArray &a = arr(g_a), &b = arr(g_b), &c = arr(g_c);
+        if (a.type != c.type || b.type != c.type) fatal("%s: types of the arrays differ", what);
+        need_hbm(a, what);
+        need_hbm(b, what);
+        need_hbm(c, what);
+        check_patch(a, alo, ahi, what);
+        check_patch(b, blo, bhi, what);
+        check_patch(c, clo, chi, what);
+        need_same_shape(a, alo, ahi, c, clo, chi, what);
+        need_same_shape(b, blo, bhi, c, clo, chi, what);
+    }
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_stat.numelem[fn]++;
+    const long *lo[2] = {alo, blo}, *hi[2] = {ahi, bhi};
+    for (int k = 0; k < 2; k++) {
+        const bool ok = same_distr(arr(use[k]), arr(g_c)) && same_patch(arr(g_c).ndim, lo[k], hi[k], clo, chi);
+        if (ok) continue;
+        char name[] = "ga_amd elem temporary";
+        tmp[k] = GA_Duplicate(g_c, name);
+        copy_patch(use[k], lo[k], hi[k], tmp[k], clo, chi, what);
+        use[k] = tmp[k];
+    }
+    GArray &c = arr(g_c);
+    const Sub sc = own_sub(c, clo, chi);
+    int zero = 0;
+    if (sc.any) {
+        const Sub sa = own_sub(arr(use[0]), clo, chi), sb = own_sub(arr(use[1]), clo, chi);
+        const int rc = gaamd_patch_elem2(c.optype, fn, sa.p, sa.stride, sb.p, sb.stride, sc.p, sc.stride, sc.count,
+                                         c.ndim, gaamd_stream());
+        if (rc == GAAMD_ZERO_DIVISOR) zero = 1;
+        else if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        g_stat.mathloc += 3 * sc.bytes;
+    }
+    math_end(what);
+    for (int k = 0; k < 2; k++)
+        if (tmp[k]) destroy(tmp[k]);
+    if (fn == GAAMD_ELEM_DIV) zero_divisor_end(zero, what);
+}
+
+static void c_elem1(int fn, int g_a, int *lo, int *hi, const void *alpha, const char *what) {
+    long flo[GA_MAX_DIM], fhi[GA_MAX_DIM];
+    if (lo) {
+        c2f_index(arr(g_a).ndim, lo, flo);
+        c2f_index(arr(g_a).ndim, hi, fhi);
+    } else {
+        whole(arr(g_a), flo, fhi);
+    }
+    elem1_patch(fn, g_a, flo, fhi, alpha, what);
+}
+
+static void c_elem2(int fn, int g_a, int *alo, int *ahi, int g_b, int *blo, int *bhi, int g_c, int *clo, int *chi,
+                    const char *what) {
+    long l[3][GA_MAX_DIM], h[3][GA_MAX_DIM];
+    const int g[3] = {g_a, g_b, g_c};
+    int *const lo[3] = {alo, blo, clo}, *const hi[3] = {ahi, bhi, chi};
+    for (int k = 0; k < 3; k++) {
+        if (lo[k]) {
+            c2f_index(arr(g[k]).ndim, lo[k], l[k]);
+            c2f_index(arr(g[k]).ndim, hi[k], h[k]);
+        } else {
+            whole(arr(g[k]), l[k], h[k]);
+        }
+    }
+    elem2_patch(fn, g_a, l[0], h[0], g_b, l[1], h[1], g_c, l[2], h[2], what);
+}
+
+void GA_Abs_value(int g_a) { c_elem1(GAAMD_ELEM_ABS, g_a, nullptr, nullptr, nullptr, "GA_Abs_value"); }
+void GA_Abs_value_patch(int g_a, int *lo, int *hi) {
+    c_elem1(GAAMD_ELEM_ABS, g_a, lo, hi, nullptr, "GA_Abs_value_patch");
+}
+void GA_Add_constant(int g_a, void *alpha) {
+    c_elem1(GAAMD_ELEM_ADD_CONST, g_a, nullptr, nullptr, alpha, "GA_Add_constant");
+}
+void GA_Add_constant_patch(int g_a, int *lo, int *hi, void *alpha) {
+    c_elem1(GAAMD_ELEM_ADD_CONST, g_a, lo, hi, alpha, "GA_Add_constant_patch");
+}
+void GA_Recip(int g_a) { c_elem1(GAAMD_ELEM_RECIP, g_a, nullptr, nullptr, nullptr, "GA_Recip"); }
+void GA_Recip_patch(int g_a, int *lo, int *hi) { c_elem1(GAAMD_ELEM_RECIP, g_a, lo, hi, nullptr, "GA_Recip_patch"); }
+
+#define GAAMD_ELEM2(NAME, FN)                                                                              \
+    void GA_Elem_##NAME(int g_a, int g_b, int g_c) {                                                       \
+        c_elem2(FN, g_a, nullptr, nullptr, g_b, nullptr, nullptr, g_c, nullptr, nullptr, "GA_Elem_" #NAME); \
+    }                                                                                                      \
+    void GA_Elem_##NAME##_patch(int g_a, int *alo, int *ahi, int g_b, int *blo, int *bhi, int g_c, int *clo, \
+                                int *chi) {                                                                \
+        c_elem2(FN, g_a, alo, ahi, g_b, blo, bhi, g_c, clo, chi, "GA_Elem_" #NAME "_patch");               \
+    }
+GAAMD_ELEM2(multiply, GAAMD_ELEM_MUL)
+GAAMD_ELEM2(divide, GAAMD_ELEM_DIV)
+GAAMD_ELEM2(maximum, GAAMD_ELEM_MAX)
+GAAMD_ELEM2(minimum, GAAMD_ELEM_MIN)
+#undef GAAMD_ELEM2
+
+// pnga_select_elem (select.c:255-470): each rank with a block selects on it, then the ranks
+// agree by gops -- the best key, the lowest row-major linear index among its holders, and
+// that element's bits summed as integers (every other rank adds zeros, so -0.0 survives).
+// armci_msg_sel_scope would break ties by rank; this rule does not depend on the block map.
+void NGA_Select_elem(int g_a, char *op, void *val, int *index) {
+    const char *what = "NGA_Select_elem";
+    GArray &a = arr(g_a);
+    if (!op || (strncmp(op, "min", 3) != 0 && strncmp(op, "max", 3) != 0))
+        fatal("%s: operator '%s' not recognized (\"min\" or \"max\")", what, op ? op : "(null)");
+    need_hbm(a, what);
+    const bool mx = strncmp(op, "max", 3) == 0;
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_stat.numselect++;
+    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
+    whole(a, lo, hi);
+    const Sub s = own_sub(a, lo, hi);
+    int bits[4] = {0, 0, 0, 0};
+    union { int i; long l; float f; double d; } key, best;
+    memset(&key, 0, sizeof(key));
+    long lin = 0;
+    if (s.any) {
+        long long li = -1;
+        const int rc = gaamd_patch_select(a.optype, mx ? 1 : 0, s.p, s.stride, s.count, a.ndim, bits, &key, &li,
+                                          gaamd_stream());
+        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        long mult = 1;
+        for (int d = 0; d < a.ndim; d++) {   // block-local, dimension 0 fastest -> whole array
+            lin += (s.plo[d] - 1 + (long)(li % s.count[d])) * mult;
+            li /= s.count[d];
+            mult *= a.dims[d];
+        }
+        g_stat.mathloc += s.bytes;
+    }
+    // the best key; a rank without a block contributes the operation's identity
+    char opname[4];
+    snprintf(opname, sizeof(opname), "%s", mx ? "max" : "min");
+    bool holder = s.any;
+    switch (a.type) {
+    case C_INT:
+        best.i = s.any ? key.i : (mx ? INT_MIN : INT_MAX);
+        armci_msg_igop(&best.i, 1, opname);
+        holder = holder && key.i == best.i;
+        break;
+    case C_LONG:
+        best.l = s.any ? key.l : (mx ? LONG_MIN : LONG_MAX);
+        armci_msg_lgop(&best.l, 1, opname);
+        holder = holder && key.l == best.l;
+        break;
+    case C_FLOAT:
+    case C_SCPL:
+        best.f = s.any ? key.f : (mx ? -HUGE_VALF : HUGE_VALF);
+        armci_msg_fgop(&best.f, 1, opname);
+        holder = holder && key.f == best.f;
+        break;
+    default:
+        best.d = s.any ? key.d : (mx ? -HUGE_VAL : HUGE_VAL);
+        armci_msg_dgop(&best.d, 1, opname);
+        holder = holder && key.d == best.d;
+        break;
+    }
+    char mn[] = "min", plus[] = "+";
+    long first = holder ? lin : LONG_MAX;
+    armci_msg_lgop(&first, 1, mn);
+    if (!(holder && lin == first)) memset(bits, 0, sizeof(bits));
+    armci_msg_igop(bits, 4, plus);
+    if (first == LONG_MAX) first = 0;   // only NaN keys: unspecified
+    memcpy(val, bits, (size_t)a.elemsize);
+    for (int d = 0; d < a.ndim; d++) {
+        index[a.ndim - 1 - d] = (int)(first % a.dims[d]);
+        first /= a.dims[d];
+    }
+}
+
 // ---- GA_Dgemm / GA_Sgemm / NGA_Matmul_patch ----------------------------------------
 // pnga_matmul (global/src/matmul.c) gets chunks of A and B to host buffers, multiplies
 // them with a host BLAS and accumulates the products into C.  Here every block is in HBM
@@ -1495,6 +1703,11 @@ void GA_Print_stats(void) {
     printf("[%d] accumulate bytes total %.0f, local %.0f (%.1f%%)\n", my_rank(), g_stat.acctot, g_stat.accloc,
            g_stat.acctot > 0 ? 100.0 * g_stat.accloc / g_stat.acctot : 0.0);
     printf("[%d] GA transposes: transpose %ld, symmetrize %ld\n", my_rank(), g_stat.numtranspose, g_stat.numsymm);
+    printf("[%d] GA element-wise calls: abs %ld, add_constant %ld, recip %ld, multiply %ld, divide %ld, maximum %ld, "
+           "minimum %ld; select %ld\n",
+           my_rank(), g_stat.numelem[GAAMD_ELEM_ABS], g_stat.numelem[GAAMD_ELEM_ADD_CONST],
+           g_stat.numelem[GAAMD_ELEM_RECIP], g_stat.numelem[GAAMD_ELEM_MUL], g_stat.numelem[GAAMD_ELEM_DIV],
+           g_stat.numelem[GAAMD_ELEM_MAX], g_stat.numelem[GAAMD_ELEM_MIN], g_stat.numselect);
 }
 
 }  // extern "C"

@@ -8,5 +8,6 @@
 #include "gaamd_iov.hip"
 #include "gaamd_misc.hip"
 #include "gaamd_patch.hip"
+#include "gaamd_select.hip"
 #include "gaamd_gemm.hip"
 #include "gaamd_transpose.hip"

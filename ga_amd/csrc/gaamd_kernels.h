@@ -133,6 +133,20 @@ int launch_patch_add(int op, const void *alpha, const void *a, const long long *
 // synchronises `stream` and writes one element to `result` (host)
 int launch_patch_dot(int op, const void *a, const long long *a_stride, const void *b, const long long *b_stride,
                      const long long *count, int ndim, void *result, hipStream_t stream);
+// element-wise algebra (global/src/elem_alg.c) on the map kernel; fn = GAAMD_ELEM_* (ga_amd.h).
+// RECIP and DIV synchronise `stream` and return kPatchZeroDivisor when an element was left
+// unwritten because its divisor is zero; the other operations return with the kernel in flight.
+enum { kElemAbs = 1, kElemAddConst = 2, kElemRecip = 3, kElemMul = 4, kElemDiv = 5, kElemMax = 6, kElemMin = 7 };
+constexpr int kPatchZeroDivisor = 2;
+int launch_patch_elem1(int op, int fn, const void *scalar, void *dst, const long long *dst_stride,
+                       const long long *count, int ndim, hipStream_t stream);
+int launch_patch_elem2(int op, int fn, const void *a, const long long *a_stride, const void *b,
+                       const long long *b_stride, void *c, const long long *c_stride, const long long *count,
+                       int ndim, hipStream_t stream);
+// the minimum (maximum) element of a patch and its linear index (gaamd_select.hip); synchronises
+// `stream`; value, key (may be null) and index are host memory.  1 and *index = -1 on a count of zero.
+int launch_patch_select(int op, int want_max, const void *a, const long long *a_stride, const long long *count,
+                        int ndim, void *value, void *key, long long *index, hipStream_t stream);
 struct PatchPlan;
 // launch_patch_add's checks without a launch (no device): 0 launch, 1 nothing to do, < 0 error;
 // plan[0..3] = {vector width, row levels after merging, rows, vectors per row}

@@ -12,6 +12,11 @@
 //                  c.im = x.re*a.im + x.im*a.re + y.re*b.im + y.im*b.re   2537-2546
 //   dot            sum += a*b; complex (no conjugate)
 //                  re += a.re*b.re - b.im*a.im; im += a.im*b.re + b.im*a.re   938-1095
+// and the element-wise algebra of global/src/elem_alg.c on the same map kernel
+// (gaamd_patch_elem1 / _elem2: abs, add constant, reciprocal, multiply, divide, maximum,
+// minimum; the operations ElAbs .. ElMaxMin below carry their line numbers).  RECIP and DIV
+// leave an element whose divisor is zero unwritten and raise a flag word in mapped pinned
+// memory, which their launchers read after synchronising the stream.
 // Integers in unsigned arithmetic (two's-complement wraparound).  FP contraction is
 // off (pragma below and -ffp-contract=off): no FMA in any of these kernels.
 //
@@ -182,6 +187,274 @@ struct PatchAddCplx {
 };
 
 // ---------------------------------------------------------------------------
+// element-wise algebra (global/src/elem_alg.c; GA_ABS / GA_MAX / GA_MIN globalp.h:55-57),
+// expression for expression.  An operation F gives one element: real(a, b, s, r) for the
+// real and integer types, cplx(ar, ai, br, bi, sr, si, re, im) for the complex ones, and
+// returns false where the reference aborts on a zero divisor (nothing is stored then).
+// Integers: sums and products in unsigned arithmetic, comparisons and quotients signed.
+template <typename T>
+__device__ __forceinline__ T el_abs(T a) {   // GA_ABS: -0.0 stays -0.0, INT_MIN wraps to itself
+    if constexpr (std::is_integral<T>::value) {
+        typedef typename std::make_unsigned<T>::type U;
+        return a >= 0 ? a : (T)((U)0 - (U)a);
+    } else {
+        return a >= 0 ? a : -a;
+    }
+}
+template <typename T> __device__ __forceinline__ T el_max(T a, T b) { return a >= b ? a : b; }
+template <typename T> __device__ __forceinline__ T el_min(T a, T b) { return a <= b ? a : b; }
+
+struct ElAbs {   // do_abs 245-336, the portable branch (no hypot)
+    static constexpr bool kCheck = false;
+    template <typename T> __device__ __forceinline__ static bool real(T a, T, T, T &r) {
+        r = el_abs(a);
+        return true;
+    }
+    template <typename R>
+    __device__ __forceinline__ static bool cplx(R ar, R ai, R, R, R, R, R &re, R &im) {
+        const R mr = el_abs(ar), mi = el_abs(ai);
+        const bool first = mr >= mi;
+        const R num = first ? ai : ar, den = first ? ar : ai, m = first ? mr : mi;
+        const R x2 = num / den;
+        R t = x2 * x2;
+        t = (R)1 + t;
+        R res;
+        if constexpr (sizeof(R) == 4) {   // as C evaluates it: sqrt and the product in double
+            const double q = (double)m * __builtin_sqrt((double)t);
+            res = (R)q;
+        } else {
+            res = m * __builtin_sqrt(t);
+        }
+        re = (first && ar == (R)0) ? (R)0 : res;
+        im = (R)0;
+        return true;
+    }
+};
+
+struct ElAddConst {   // do_add_const 524-574
+    static constexpr bool kCheck = false;
+    template <typename T> __device__ __forceinline__ static bool real(T a, T, T s, T &r) {
+        if constexpr (std::is_integral<T>::value) {
+            typedef typename std::make_unsigned<T>::type U;
+            r = (T)((U)a + (U)s);
+        } else {
+            r = a + s;
+        }
+        return true;
+    }
+    template <typename R>
+    __device__ __forceinline__ static bool cplx(R ar, R ai, R, R, R sr, R si, R &re, R &im) {
+        re = ar + sr;
+        im = ai + si;
+        return true;
+    }
+};
+
+struct ElRecip {   // do_recip 338-522
+    static constexpr bool kCheck = true;
+    template <typename T> __device__ __forceinline__ static bool real(T a, T, T, T &r) {
+        if (a == (T)0) return false;
+        if constexpr (std::is_integral<T>::value) r = a == (T)1 ? (T)1 : a == (T)-1 ? (T)-1 : (T)0;   // 1 / a
+        else r = (T)1 / a;
+        return true;
+    }
+    template <typename R>
+    __device__ __forceinline__ static bool cplx(R x1, R x2, R, R, R, R, R &re, R &im) {
+        const R magr = el_abs(x1), magi = el_abs(x2);
+        const bool first = magr >= magi;
+        if (first && !(magr != (R)0)) return false;
+        const R num = first ? x2 : x1, den = first ? x1 : x2;
+        const R c = num / den;
+        R t = c * c;
+        t = (R)1 + t;
+        t = t * den;
+        const R d = (R)1 / t;
+        const R cd = first ? (-c) * d : c * d;
+        re = first ? d : cd;
+        im = first ? cd : -d;
+        return true;
+    }
+};
+
+struct ElMul {   // do_multiply 1068-1086, assign_mul_reg / _cpl
+    static constexpr bool kCheck = false;
+    template <typename T> __device__ __forceinline__ static bool real(T a, T b, T, T &r) {
+        if constexpr (std::is_integral<T>::value) {
+            typedef typename std::make_unsigned<T>::type U;
+            r = (T)((U)a * (U)b);
+        } else {
+            r = a * b;
+        }
+        return true;
+    }
+    template <typename R>
+    __device__ __forceinline__ static bool cplx(R ar, R ai, R br, R bi, R, R, R &re, R &im) {
+        R p1 = ar * br;
+        R p2 = ai * bi;
+        re = p1 - p2;
+        R p3 = ar * bi;
+        R p4 = ai * br;
+        im = p3 + p4;
+        return true;
+    }
+};
+
+struct ElDiv {   // do_divide 1136-1266; complex: every intermediate a double, for C_SCPL too
+    static constexpr bool kCheck = true;
+    template <typename T> __device__ __forceinline__ static bool real(T a, T b, T, T &r) {
+        if (b == (T)0) return false;
+        if constexpr (std::is_integral<T>::value) {
+            typedef typename std::make_unsigned<T>::type U;
+            r = b == (T)-1 ? (T)((U)0 - (U)a) : a / b;   // INT_MIN / -1 wraps to INT_MIN
+        } else {
+            r = a / b;
+        }
+        return true;
+    }
+    template <typename R>
+    __device__ __forceinline__ static bool cplx(R ar, R ai, R br, R bi, R, R, R &re, R &im) {
+        const double aReal = ar, aImag = ai, bReal = br, bImag = bi;
+        const bool first = el_abs(bReal) >= el_abs(bImag);
+        if (first && !(bReal != 0.0)) return false;
+        const double num = first ? bImag : bReal, den = first ? bReal : bImag;
+        const double x1 = num / den;
+        double t = x1 * x1;
+        t = 1.0 + t;
+        t = den * t;
+        const double x2 = 1.0 / t;
+        const double u = (first ? aImag : aReal) * x1;   // aImag*x1 | aReal*x1
+        const double v = (first ? aReal : aImag) * x1;   // aReal*x1 | aImag*x1
+        const double nr = first ? aReal + u : u + aImag;
+        const double ni = first ? aImag - v : v - aReal;
+        re = (R)(nr * x2);
+        im = (R)(ni * x2);
+        return true;
+    }
+};
+
+template <bool MAX>
+struct ElMaxMin {   // do_maximum 1533-1625, do_minimum 1628-1720
+    static constexpr bool kCheck = false;
+    template <typename T> __device__ __forceinline__ static bool real(T a, T b, T, T &r) {
+        r = MAX ? el_max(a, b) : el_min(a, b);
+        return true;
+    }
+    template <typename R>
+    __device__ __forceinline__ static bool cplx(R ar, R ai, R br, R bi, R, R, R &re, R &im) {
+        double aReal = ar, aImag = ai, bReal = br, bImag = bi;
+        double x1 = el_max(el_abs(aReal), el_abs(aImag));
+        const double x2 = el_max(el_abs(bReal), el_abs(bImag));
+        x1 = el_max(x1, x2);
+        bool take_a = true;
+        if (!(x1 == 0.0)) {
+            x1 = 1.0 / x1;
+            aReal = aReal * x1;
+            aImag = aImag * x1;
+            bReal = bReal * x1;
+            bImag = bImag * x1;
+            double p1 = aReal * aReal, p2 = aImag * aImag, p3 = bReal * bReal, p4 = bImag * bImag;
+            const double temp1 = p1 + p2, temp2 = p3 + p4;
+            take_a = MAX ? temp1 > temp2 : temp1 < temp2;
+        }
+        re = take_a ? ar : br;
+        im = take_a ? ai : bi;
+        return true;
+    }
+};
+
+// F over the W / sizeof(T) elements of a vector.  KIN = 1: dst = F(dst) in place; KIN = 2:
+// c = F(a, b).  `bad` receives bit i for element i of the vector when F refused it.
+template <class F, typename T, int KIN>
+struct PatchElemReal {
+    static constexpr int kOps = KIN == 1 ? 1 : 3, kIn = KIN, kElem = (int)sizeof(T);
+    static constexpr bool kCheck = F::kCheck;
+    T s;
+    uint32_t *flag;   // kCheck: mapped pinned word, set to 1 by every lane that meets a zero divisor
+    template <int W>
+    __device__ __forceinline__ typename Vec<W>::T apply(typename Vec<W>::T av, typename Vec<W>::T bv,
+                                                        uint32_t &bad) const {
+        constexpr int N = W / (int)sizeof(T);
+        union { typename Vec<W>::T v; T t[N]; } a, b;
+        a.v = av;
+        b.v = bv;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            T r = a.t[i];
+            if (!F::real(a.t[i], b.t[i], s, r)) bad |= 1u << i;
+            a.t[i] = r;
+        }
+        return a.v;
+    }
+    template <int W>
+    __device__ __forceinline__ typename Vec<W>::T apply(typename Vec<W>::T av, typename Vec<W>::T bv) const {
+        uint32_t bad = 0;
+        return apply<W>(av, bv, bad);
+    }
+};
+
+template <class F, typename R, int KIN>
+struct PatchElemCplx {
+    static constexpr int kOps = KIN == 1 ? 1 : 3, kIn = KIN, kElem = 2 * (int)sizeof(R);
+    static constexpr bool kCheck = F::kCheck;
+    R sr, si;
+    uint32_t *flag;
+    template <int W>
+    __device__ __forceinline__ typename Vec<W>::T apply(typename Vec<W>::T av, typename Vec<W>::T bv,
+                                                        uint32_t &bad) const {
+        constexpr int N = W / (int)(2 * sizeof(R));
+        union { typename Vec<W>::T v; R t[2 * N]; } a, b;
+        a.v = av;
+        b.v = bv;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            R re = a.t[2 * i], im = a.t[2 * i + 1];
+            if (!F::cplx(a.t[2 * i], a.t[2 * i + 1], b.t[2 * i], b.t[2 * i + 1], sr, si, re, im)) bad |= 1u << i;
+            a.t[2 * i] = re;
+            a.t[2 * i + 1] = im;
+        }
+        return a.v;
+    }
+    template <int W>
+    __device__ __forceinline__ typename Vec<W>::T apply(typename Vec<W>::T av, typename Vec<W>::T bv) const {
+        uint32_t bad = 0;
+        return apply<W>(av, bv, bad);
+    }
+};
+
+// an operation whose apply() may refuse elements (RECIP, DIV) declares kCheck = true
+template <class OP, class = void> struct op_checks { static constexpr bool value = false; };
+template <class OP> struct op_checks<OP, std::void_t<decltype(OP::kCheck)>> { static constexpr bool value = OP::kCheck; };
+
+template <typename A> __device__ __forceinline__ void store_sys(A *p, A v);
+
+// one result vector to memory.  A checking operation stores only the elements it computed:
+// a refused element keeps its bytes (a vector of more than one element is W-aligned, so its
+// elements are naturally aligned) and the lane raises the flag word.
+template <class OP, int W>
+__device__ __forceinline__ void map_store(char *o, const OP &op, typename Vec<W>::T a, typename Vec<W>::T b) {
+    typedef typename Vec<W>::T V;
+    if constexpr (op_checks<OP>::value) {
+        uint32_t bad = 0;
+        const V r = op.template apply<W>(a, b, bad);
+        if (bad == 0) {
+            vstore<W, true>(o, r);
+            return;
+        }
+        constexpr int E = OP::kElem, N = W / E;
+        if constexpr (N > 1) {
+            union { V v; typename Vec<E>::T e[N]; } u;
+            u.v = r;
+#pragma unroll
+            for (int i = 0; i < N; ++i)
+                if (!((bad >> i) & 1u)) vstore<E, true>(o + i * E, u.e[i]);
+        }
+        store_sys(op.flag, 1u);
+    } else {
+        vstore<W, true>(o, op.template apply<W>(a, b));
+    }
+}
+
+// ---------------------------------------------------------------------------
 // MAP kernel: block (x, y) = chunk x of row row0 + y
 template <class OP, int W, int U, int BS, int LV>
 __global__ __launch_bounds__(BS) void k_patch_map(const PatchDesc d, const OP op) {
@@ -206,7 +479,7 @@ __global__ __launch_bounds__(BS) void k_patch_map(const PatchDesc d, const OP op
             else y[k] = x[k];
         }
 #pragma unroll
-        for (int k = 0; k < U; ++k) vstore<W, true>(o + (int64_t)k * BS * W, op.template apply<W>(x[k], y[k]));
+        for (int k = 0; k < U; ++k) map_store<OP, W>(o + (int64_t)k * BS * W, op, x[k], y[k]);
         return;
     }
     for (int k = 0; k < U; ++k) {   // row tail: one vector at a time
@@ -214,7 +487,7 @@ __global__ __launch_bounds__(BS) void k_patch_map(const PatchDesc d, const OP op
         V a = V{}, b = V{};
         if constexpr (OP::kIn >= 1) a = vload<W, true>(i1 + (int64_t)k * BS * W);
         if constexpr (OP::kIn == 2) b = vload<W, true>(i2 + (int64_t)k * BS * W);
-        vstore<W, true>(o + (int64_t)k * BS * W, op.template apply<W>(a, b));
+        map_store<OP, W>(o + (int64_t)k * BS * W, op, a, b);
     }
 }
 
@@ -656,7 +929,10 @@ int launch_patch_add(int op, const void *alpha, const void *a, const long long *
 
 // ---------------------------------------------------------------------------
 // dot: per-thread scratch (the partials in HBM, the result in mapped pinned memory),
-// grown on demand, freed by patch_release() at comex_finalize
+// grown on demand, freed by patch_release() at comex_finalize.  The pinned block also holds
+// what select returns (gaamd_select.hip: the element at 0, its key at kResKey, its index
+// at kResIndex) and the zero-divisor flag of RECIP / DIV (kResFlag).
+constexpr size_t kResBytes = 128, kResKey = 16, kResIndex = 24, kResFlag = 64;
 struct DotScratch {
     int dev = -1;
     void *part = nullptr;
@@ -691,7 +967,8 @@ static DotScratch *dot_scratch(size_t bytes) {
     if (s.dev != dev) dot_scratch_free(s);
     s.dev = dev;
     if (!s.res_host) {
-        if (hipHostMalloc(&s.res_host, 16, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) return nullptr;
+        if (hipHostMalloc(&s.res_host, kResBytes, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess)
+            return nullptr;
         if (hipHostGetDevicePointer(&s.res_dev, s.res_host, 0) != hipSuccess) return nullptr;
     }
     if (s.part_bytes < bytes) {
@@ -769,6 +1046,84 @@ int launch_patch_dot(int op, const void *a, const long long *a_stride, const voi
     if (e != hipSuccess) return rc_of(e);
     memcpy(result, s->res_host, (size_t)p.esz);
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// element-wise algebra: the map kernel with the operations above
+template <class F, int KIN>
+static hipError_t go_elem(int op, const PatchDesc &d, const PatchPlan &p, const void *s, uint32_t *flag,
+                          hipStream_t st) {
+    const double zero[2] = {0.0, 0.0};
+    if (!s) s = zero;
+    switch (op) {
+    case 37:
+        return go_map_w<PatchElemReal<F, int32_t, KIN>, 4>(d, p, PatchElemReal<F, int32_t, KIN>{rd<int32_t>(s), flag}, st);
+    case 38:
+        return go_map_w<PatchElemReal<F, double, KIN>, 8>(d, p, PatchElemReal<F, double, KIN>{rd<double>(s), flag}, st);
+    case 39:
+        return go_map_w<PatchElemReal<F, float, KIN>, 4>(d, p, PatchElemReal<F, float, KIN>{rd<float>(s), flag}, st);
+    case 40:
+        return go_map_w<PatchElemCplx<F, float, KIN>, 8>(
+            d, p, PatchElemCplx<F, float, KIN>{rd<float>(s), rd<float>(s, 1), flag}, st);
+    case 41:
+        return go_map_w<PatchElemCplx<F, double, KIN>, 16>(
+            d, p, PatchElemCplx<F, double, KIN>{rd<double>(s), rd<double>(s, 1), flag}, st);
+    case 42:
+        return go_map_w<PatchElemReal<F, int64_t, KIN>, 8>(d, p, PatchElemReal<F, int64_t, KIN>{rd<int64_t>(s), flag}, st);
+    }
+    return hipErrorInvalidValue;
+}
+
+// RECIP and DIV: the flag word cleared before the launch, read after the stream has finished
+template <class F, int KIN>
+static int go_elem_checked(int op, const PatchDesc &d, const PatchPlan &p, hipStream_t stream) {
+    DotScratch *s = dot_scratch(0);
+    if (!s) return -100 - (int)hipGetLastError();
+    volatile uint32_t *flag = (volatile uint32_t *)((char *)s->res_host + kResFlag);
+    *flag = 0;
+    hipError_t e = go_elem<F, KIN>(op, d, p, nullptr, (uint32_t *)((char *)s->res_dev + kResFlag), stream);
+    if (e != hipSuccess) return rc_of(e);
+    e = stream ? hipStreamSynchronize(stream) : hipDeviceSynchronize();
+    if (e != hipSuccess) return rc_of(e);
+    return *flag ? kPatchZeroDivisor : 0;
+}
+
+int launch_patch_elem1(int op, int fn, const void *scalar, void *dst, const long long *dst_stride,
+                       const long long *count, int ndim, hipStream_t stream) {
+    PatchPlan p;
+    const void *base[1] = {dst};
+    const long long *str[1] = {dst_stride};
+    const int rc = patch_plan(op, 1, base, str, count, ndim, p);
+    if (rc < 0) return rc;
+    if (fn != kElemAbs && fn != kElemAddConst && fn != kElemRecip) return kPatchErrOp;
+    if (rc) return 0;
+    if (fn == kElemAddConst && !scalar) return kPatchErrScalar;
+    PatchDesc d;
+    fill_desc(d, p, 1, base);
+    switch (fn) {
+    case kElemAbs: return rc_of(go_elem<ElAbs, 1>(op, d, p, nullptr, nullptr, stream));
+    case kElemAddConst: return rc_of(go_elem<ElAddConst, 1>(op, d, p, scalar, nullptr, stream));
+    default: return go_elem_checked<ElRecip, 1>(op, d, p, stream);
+    }
+}
+
+int launch_patch_elem2(int op, int fn, const void *a, const long long *a_stride, const void *b,
+                       const long long *b_stride, void *c, const long long *c_stride, const long long *count,
+                       int ndim, hipStream_t stream) {
+    PatchPlan p;
+    const int rc = plan_patch_add(op, a, a_stride, b, b_stride, c, c_stride, count, ndim, nullptr, &p);
+    if (rc < 0) return rc;
+    if (fn != kElemMul && fn != kElemDiv && fn != kElemMax && fn != kElemMin) return kPatchErrOp;
+    if (rc) return 0;
+    const void *base[3] = {c, a, b};
+    PatchDesc d;
+    fill_desc(d, p, 3, base);
+    switch (fn) {
+    case kElemMul: return rc_of(go_elem<ElMul, 2>(op, d, p, nullptr, nullptr, stream));
+    case kElemMax: return rc_of(go_elem<ElMaxMin<true>, 2>(op, d, p, nullptr, nullptr, stream));
+    case kElemMin: return rc_of(go_elem<ElMaxMin<false>, 2>(op, d, p, nullptr, nullptr, stream));
+    default: return go_elem_checked<ElDiv, 2>(op, d, p, stream);
+    }
 }
 
 }  // namespace gaamd

@@ -101,6 +101,22 @@ int gaamd_patch_add_plan(int op, const void *a, const long long *a_stride, const
     return plan_patch_add(op, a, a_stride, b, b_stride, c, c_stride, count, ndim, plan);
 }
 
+int gaamd_patch_elem1(int op, int fn, const void *scalar, void *dst, const long long *dst_stride,
+                      const long long *count, int ndim, void *stream) {
+    return launch_patch_elem1(op, fn, scalar, dst, dst_stride, count, ndim, stream_of(stream));
+}
+
+int gaamd_patch_elem2(int op, int fn, const void *a, const long long *a_stride, const void *b,
+                      const long long *b_stride, void *c, const long long *c_stride, const long long *count, int ndim,
+                      void *stream) {
+    return launch_patch_elem2(op, fn, a, a_stride, b, b_stride, c, c_stride, count, ndim, stream_of(stream));
+}
+
+int gaamd_patch_select(int op, int want_max, const void *a, const long long *a_stride, const long long *count,
+                       int ndim, void *value, void *key, long long *index, void *stream) {
+    return launch_patch_select(op, want_max, a, a_stride, count, ndim, value, key, index, stream_of(stream));
+}
+
 int gaamd_gemm(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
                const void *a, long long lda, const void *b, long long ldb, const void *beta, void *c, long long ldc,
                void *stream) {

@@ -173,6 +173,54 @@ int gaamd_ga_gemm_panel(void);
    in a host segment (both). */
 void GA_Transpose(int g_a, int g_b);
 void GA_Symmetrize(int g_a);
+/* Element-wise algebra and element selection on HBM blocks (capi.c GA_Abs_value ...
+   GA_Elem_minimum_patch -> global/src/elem_alg.c; NGA_Select_elem -> global/src/select.c).
+   Collective, with the reference's syncs; each rank runs one gfx950 kernel on its own part
+   of the patch (ga_amd.h gaamd_patch_elem1 / _elem2 / _select), the reference's arithmetic
+   expression for expression (listed there).  All six types.
+     GA_Abs_value       a = |a|              GA_Elem_multiply   c = a * b
+     GA_Add_constant    a = a + *alpha       GA_Elem_divide     c = a / b
+     GA_Recip           a = 1 / a            GA_Elem_maximum / _minimum   c = max / min(a, b)
+   The unary calls work in place like NGA_Scale_patch.  The binary calls follow NGA_Add_patch:
+   equal block maps with equal patches are computed in place (g_c may be g_a and / or g_b, so
+   GA_Elem_multiply(g_a, g_b, g_a) is legal); any other combination goes through GA_Duplicate
+   temporaries and NGA_Copy_patch (ngai_elem2_patch_, elem_alg.c:1886-1930), destroyed before
+   return.
+   Departure 1, complex GA_Abs_value: the reference uses hypot() where the C library has it.
+   The host's and the device's hypot are different functions, so the reference's portable
+   branch (the larger part times sqrt(1 + ratio^2)) is used instead: it is the only one whose
+   bits can be reproduced anywhere.
+   Zero divisors (GA_Recip, GA_Elem_divide): the reference aborts at the first one.  Here the
+   kernel leaves such elements unwritten and writes all others; after it has completed the
+   ranks combine their flags and, if any is set, EVERY rank ends through GA_Error ("zero
+   divisor"), so none is left waiting in a barrier.
+   NGA_Select_elem(g_a, "min" | "max", val, index): the smallest / largest element (complex:
+   by re*re + im*im in the element's real type), its bits in *val and its C subscripts in
+   index[].  Syncs on entry (select.c:268-270).
+   Departure 2, ties: the result is the best key over all ranks and, among equal keys, the
+   element of the lowest row-major (C order) linear index in the whole array -- the
+   reference's first occurrence on one rank, and, unlike the reference (whose
+   armci_msg_sel_scope breaks ties by rank), the same answer on any number of ranks and any
+   block map, as the dot products and gemm are.  Of +0 and -0 the one that comes first is
+   returned, with its sign.  An array that holds a NaN returns an unspecified element.
+   Aborts through GA_Error, before the first sync or launch: types that differ, a patch out
+   of range, patches of different rank or extents, an array in a host segment; an op that is
+   neither "min" nor "max". */
+void GA_Abs_value(int g_a);
+void GA_Abs_value_patch(int g_a, int *lo, int *hi);
+void GA_Add_constant(int g_a, void *alpha);
+void GA_Add_constant_patch(int g_a, int *lo, int *hi, void *alpha);
+void GA_Recip(int g_a);
+void GA_Recip_patch(int g_a, int *lo, int *hi);
+void GA_Elem_multiply(int g_a, int g_b, int g_c);
+void GA_Elem_divide(int g_a, int g_b, int g_c);
+void GA_Elem_maximum(int g_a, int g_b, int g_c);
+void GA_Elem_minimum(int g_a, int g_b, int g_c);
+void GA_Elem_multiply_patch(int g_a, int *alo, int *ahi, int g_b, int *blo, int *bhi, int g_c, int *clo, int *chi);
+void GA_Elem_divide_patch(int g_a, int *alo, int *ahi, int g_b, int *blo, int *bhi, int g_c, int *clo, int *chi);
+void GA_Elem_maximum_patch(int g_a, int *alo, int *ahi, int g_b, int *blo, int *bhi, int g_c, int *clo, int *chi);
+void GA_Elem_minimum_patch(int g_a, int *alo, int *ahi, int g_b, int *blo, int *bhi, int g_c, int *clo, int *chi);
+void NGA_Select_elem(int g_a, char *op, void *val, int *index);
 /* global arrays alive on this rank (temporaries of the general path are destroyed
    before their call returns) */
 int gaamd_ga_live_arrays(void);

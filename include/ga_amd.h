@@ -93,6 +93,59 @@ int gaamd_patch_dot  (int op, const void *a, const long long *a_stride, const vo
 int gaamd_patch_add_plan(int op, const void *a, const long long *a_stride, const void *b,
                          const long long *b_stride, const void *c, const long long *c_stride,
                          const long long *count, int ndim, long long plan[4]);
+/* Element-wise algebra on a patch where it lies: the loops of global/src/elem_alg.c (GA_ABS /
+ * GA_MAX / GA_MIN of globalp.h:55-57), expression for expression, no FMA, on gaamd_patch_add's
+ * map kernel.  Geometry, checks and negative codes are those of gaamd_patch_scale (elem1, in
+ * place on dst) and gaamd_patch_add (elem2, c = fn(a, b); c may be exactly a and/or b, any other
+ * overlap is -11); an unknown fn is -4, a missing scalar for ADD_CONST -5; a count of zero: 0,
+ * no launch.  All six types; integer sums and products in unsigned (wraparound) arithmetic.
+ *   ABS        x >= 0 ? x : -x (not fabs: -0.0 stays -0.0, INT_MIN / LONG_MIN wrap to
+ *              themselves).  Complex: the reference's portable branch (do_abs without
+ *              HAVE_HYPOT, 270-288 / 297-315), the larger part times sqrt(1 + ratio^2), imag = 0
+ *              -- NOT hypot: the host's and the device's hypot are different functions, only
+ *              this branch has the same bits everywhere.  C_SCPL as C evaluates it: ratio and
+ *              1 + ratio^2 in float, sqrt and the product in double, one rounding on the store.
+ *   ADD_CONST  x += *scalar; complex: real and imaginary part each              524-574
+ *   RECIP      1 / x; complex: the scaled form 399-425 (C_SCPL entirely in float, 454-480)
+ *   MUL        a * b; complex re = a.re*b.re - a.im*b.im, im = a.re*b.im + a.im*b.re
+ *   DIV        a / b (INT_MIN / -1, undefined in C, is the wrapped INT_MIN); complex: the
+ *              scaled form 1177-1194, for C_SCPL with every intermediate a double   1136-1266
+ *   MAX, MIN   a >= b ? a : b, a <= b ? a : b (with a NaN: b; +0 against -0: a).  Complex:
+ *              squared moduli after scaling by 1 / max|parts|, in double; MAX takes a only if
+ *              |a|^2 > |b|^2, MIN only if <, a tie gives b, both zero gives a      1533-1720
+ * Zero divisors (RECIP: x == 0, so -0.0 too, complex both parts zero; DIV: b == 0, complex
+ * b.re == 0 where |b.re| >= |b.im|): the reference aborts at the first one.  Here that element
+ * is left unwritten, every other element is written, and the call returns GAAMD_ZERO_DIVISOR.
+ * RECIP and DIV therefore synchronise their stream before they return; the other five return
+ * with the kernel in flight, like gaamd_patch_add. */
+#define GAAMD_ELEM_ABS 1         /* fn of gaamd_patch_elem1 */
+#define GAAMD_ELEM_ADD_CONST 2
+#define GAAMD_ELEM_RECIP 3
+#define GAAMD_ELEM_MUL 4         /* fn of gaamd_patch_elem2 */
+#define GAAMD_ELEM_DIV 5
+#define GAAMD_ELEM_MAX 6
+#define GAAMD_ELEM_MIN 7
+#define GAAMD_ZERO_DIVISOR 2
+int gaamd_patch_elem1(int op, int fn, const void *scalar /* ADD_CONST only */, void *dst,
+                      const long long *dst_stride, const long long *count, int ndim, void *stream);
+int gaamd_patch_elem2(int op, int fn, const void *a, const long long *a_stride, const void *b,
+                      const long long *b_stride, void *c, const long long *c_stride,
+                      const long long *count, int ndim, void *stream);
+/* The minimum (want_max != 0: maximum) element of a patch and its position; the kernel under
+ * NGA_Select_elem (select.c:143-250).  Key: the element itself; complex re*re + im*im in the
+ * element's own real type (two products, one sum).  `value` receives the element's bits (for
+ * complex the element, not the key), `key` (may be NULL) the compared quantity, `index` the
+ * element's linear index in the patch with count[0] fastest.  Among equal keys the lowest index
+ * wins (the reference's first occurrence; of +0 and -0 the one that comes first), whatever the
+ * grid: two launches, partials in device scratch, no atomics; the same input gives the same
+ * answer on every run.  A patch that holds a NaN returns an unspecified element (the
+ * reference's answer depends on where the NaN lies).  Synchronises its stream, like
+ * gaamd_patch_dot, whose geometry, checks and codes it has (-5: value or index missing).
+ * A count of zero: returns 1 and *index = -1, nothing launched. */
+int gaamd_patch_select(int op, int want_max, const void *a, const long long *a_stride,
+                       const long long *count, int ndim, void *value /* host, one element */,
+                       void *key /* host, may be NULL: the compared quantity */,
+                       long long *index /* host */, void *stream);
 /* Row-major GEMM on the gfx950 matrix cores, for op = COMEX_ACC_DBL (v_mfma_f64_16x16x4_f64)
  * and COMEX_ACC_FLT (v_mfma_f32_16x16x4_f32); the kernel under GA_Dgemm / GA_Sgemm (ga.h):
  *   C[i][j] = alpha * sum_k op(A)[i][k] * op(B)[k][j] + beta * C[i][j],  i < m, j < n, kk < k
