@@ -5,6 +5,8 @@ Modes:
   all         whole-array calls, patch forms, the general path, ordering against a
               pending NGA_NbAcc -- each section prints "SECTION <name> OK"
   big         a 1-D C_DBL array of 2**29 + 3 elements: 64-bit offsets
+  tall        C_DBL and C_FLOAT arrays of [70001 * ranks + 1, 3]: every rank's part of the
+              patch has more than 65535 rows, so the map kernels take a second launch
   abort-type / abort-trans / abort-host
               a call that must end the process through GA_Error; prints
               "ABORT EXPECTED" just before it and "NOT REACHED" if it returns
@@ -321,6 +323,51 @@ def big(L, rank, size):
     L.GA_Destroy(g)
 
 
+def tall(L, rank, size):
+    """a patch of two of the three columns without the first and the last row: rows of two
+    elements, more than 65535 of them on every rank (go_map's second launch, row0 != 0)"""
+    rows = 70001 * size + 1
+    dims = [rows, 3]
+    n = rows * 3
+    lo, hi = [1, 0], [rows - 2, 1]
+    s = sl(lo, hi)
+    for t in (C_DBL, C_FLOAT):
+        op = OP_OF[t]
+        rng = np.random.default_rng(31 * t)
+        a, b, c = (GA(L, t, dims, nm) for nm in (b"a", b"b", b"c"))
+        mylo, myhi = blocks_of(L, a.g, 2, size)[rank]
+        own = min(myhi[0], hi[0]) - max(mylo[0], lo[0]) + 1
+        assert own > 65535 and mylo[1] <= lo[1] and myhi[1] >= hi[1], (mylo, myhi, own)
+        tag = f"{ga_amd.OP_NAME[op]} {dims} {lo}..{hi}"
+        shape = a.model[s].shape
+        val, al, be = K.scalar(op, K.VALUE[op]), K.scalar(op, K.ALPHA[op]), K.scalar(op, K.BETA[op])
+        a.put(K.gen(op, n, rng), rank)
+        b.put(K.gen(op, n, rng), rank)
+        c.put(K.gen(op, n, rng), rank)
+        L.NGA_Fill_patch(c.g, ia(lo), ia(hi), vp(val))
+        c.model[s] = K.scalar(op, K.VALUE[op])[0]
+        c.check(f"NGA_Fill_patch {tag}")
+        L.NGA_Scale_patch(a.g, ia(lo), ia(hi), vp(al))
+        a.model[s] = K.ref_scale(op, flat(a.model[s]), K.ALPHA[op]).reshape(shape)
+        a.check(f"NGA_Scale_patch {tag}")
+        L.NGA_Add_patch(vp(al), a.g, ia(lo), ia(hi), vp(be), b.g, ia(lo), ia(hi), c.g, ia(lo), ia(hi))
+        c.model[s] = K.ref_add(op, K.ALPHA[op], flat(a.model[s]), K.BETA[op], flat(b.model[s])).reshape(shape)
+        c.check(f"NGA_Add_patch {tag}")
+        a.check(f"NGA_Add_patch left a alone {tag}")
+        b.check(f"NGA_Add_patch left b alone {tag}")
+        a.put(K.gen(op, n, rng, 5), rank)   # f32: 25 * 2 * (rows - 2) < 2**24, every sum exact
+        b.put(K.gen(op, n, rng, 5), rank)
+        got = dot_call(L, t, a.g, b.g, (lo, hi, lo, hi))
+        want = K.ref_dot_exact(op, flat(a.model[s]), flat(b.model[s]))
+        assert got.tobytes() == want.tobytes(), (f"NGA_{DOT_OF[t]}dot_patch {tag}", got, want)
+        say_dot(f"tall-{ga_amd.OP_NAME[op]}", got)
+        L.GA_Fill(c.g, vp(val))
+        c.model = K.ref_fill(op, n, K.VALUE[op]).reshape(dims)
+        c.check(f"GA_Fill {tag}")
+        for x in (a, b, c):
+            x.destroy()
+
+
 def aborts(L, rank, size, mode):
     dims = [20, 30]
     if mode == "abort-type":
@@ -351,6 +398,8 @@ def main():
         sys.exit(3)
     if mode == "big":
         big(L, rank, size)
+    elif mode == "tall":
+        tall(L, rank, size)
     else:
         for name, fn in (("whole", whole_array), ("patch", patch_forms), ("general", general_path),
                          ("order", ordering)):

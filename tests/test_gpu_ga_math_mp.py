@@ -102,6 +102,20 @@ def test_ga_math_64bit_offsets():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 2])
+def test_ga_math_tall_arrays(n):
+    """C_DBL and C_FLOAT arrays of [70001 * n + 1, 3]: NGA_Fill_patch, NGA_Scale_patch,
+    NGA_Add_patch and the dot products on a patch of which every rank holds more than 65535
+    rows of two elements (the worker asserts it), and GA_Fill on the whole array; the
+    comparison covers the column outside the patch and the first and last rows"""
+    outs = launch_ok("tall", n)
+    dots = [[ln for ln in out.splitlines() if ln.startswith("DOT ")] for out in outs]
+    assert len(dots[0]) == 2, dots[0]
+    for d in dots[1:]:
+        assert d == dots[0], (d, dots[0])
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("mode,message,env", [
     ("abort-type", "type mismatch", None),
     ("abort-trans", "transposed patches", None),
