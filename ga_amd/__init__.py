@@ -217,6 +217,39 @@ def patch_select(op, want_max, a, a_stride, count, stream=None):
     return rc, val, key, idx.value
 
 
+# GA's matrix.c calls at kernel level (gaamd_patch_norm / _diagonal / _scale_rows / _scale_cols);
+# the return code is handed back (0, or the negative codes of ga_amd.h)
+GAAMD_NORM_ONE, GAAMD_NORM_INF = 1, 2
+GAAMD_DIAG_GET, GAAMD_DIAG_SET, GAAMD_DIAG_ADD, GAAMD_DIAG_SHIFT, GAAMD_DIAG_ZERO = 1, 2, 3, 4, 5
+
+
+def patch_norm(op, kind, a, a_stride, count, stream=None):
+    """(return code, the norm as a one-element numpy array of the op's type, complex: its real type)"""
+    out = np.zeros(1, dtype=np.zeros(1, dtype=OP_DTYPE.get(op, np.float64)).real.dtype)
+    out.view(np.uint8)[:] = 0xA5   # the call has to write it, the zero of an empty patch too
+    rc = lib().gaamd_patch_norm(op, kind, ctypes.c_void_p(a), ll_array(a_stride), ll_array(count), len(count),
+                                out.ctypes.data_as(ctypes.c_void_p), stream)
+    return rc, out
+
+
+def diag(op, fn, n, a, a_step, v, v_step, scalar=None, stream=None):
+    """gaamd_diagonal: n elements at a + i * a_step and v + i * v_step (bytes); v of None or 0 and
+    scalar of None reach the library as NULL"""
+    keep, sp = scale_buffer(op, scalar) if scalar is not None else (None, None)
+    return lib().gaamd_diagonal(op, fn, n, ctypes.c_void_p(a), a_step, ctypes.c_void_p(v) if v else None, v_step,
+                                sp, stream)
+
+
+def scale_rows(op, rows, cols, a, lda, v, stream=None):
+    """a[i][j] *= v[i] in place; lda in elements; complex part by part"""
+    return lib().gaamd_scale_rows(op, rows, cols, ctypes.c_void_p(a), lda, ctypes.c_void_p(v) if v else None, stream)
+
+
+def scale_cols(op, rows, cols, a, lda, v, stream=None):
+    """a[i][j] *= v[j] in place; lda in elements; complex part by part"""
+    return lib().gaamd_scale_cols(op, rows, cols, ctypes.c_void_p(a), lda, ctypes.c_void_p(v) if v else None, stream)
+
+
 def patch_add_plan(op, a, a_stride, b, b_stride, c, c_stride, count):
     """gaamd_patch_add's checks without a launch (no GPU): (code, {width, levels, rows, nvec})"""
     out = (ctypes.c_longlong * 4)()

@@ -90,6 +90,7 @@ static struct {
     long numtranspose = 0, numsymm = 0;
     long numelem[8] = {0};   // by GAAMD_ELEM_* code
     long numselect = 0;
+    long numdiag = 0, numscalerows = 0, numscalecols = 0, numnorm1 = 0, numnorminf = 0;
     double mathloc = 0;
 } g_stat;
 
@@ -1693,6 +1694,148 @@ void GA_Symmetrize(int g_a) {
     math_end(what);
 }
 
+// ---- diagonals, row / column scaling, norms (global/src/matrix.c) ------------------------
+// The reference fetches the part of g_v a rank's block needs into a host buffer and loops over
+// the block on the host.  Here the owner of g_a computes in HBM: the part of g_v is used in
+// place where it lies in the rank's own block of g_v, and goes through HBM scratch and
+// NGA_Get's / NGA_Put's path otherwise (as get_mirror does for the transposes).
+// Internally (Fortran order) index 0 runs along a stored row: C subscript j is index 0, C
+// subscript i is index 1; a block is count[1] rows of count[0] with ext[0] between rows.
+enum VecUse { V_NONE, V_READ, V_WRITE };
+
+// elements [lo, hi] (1-based) of the 1-D array g_v for this rank's kernel: its own block in
+// place, or scratch (filled by a get for V_READ)
+struct VecPart {
+    void *p = nullptr, *scratch = nullptr;
+};
+static VecPart vec_part(int g_v, long lo, long hi, VecUse use, const char *what) {
+    VecPart r;
+    GArray &v = arr(g_v);
+    const Sub sv = own_sub(v, &lo, &hi);
+    if (sv.any && sv.count[0] == hi - lo + 1) {
+        r.p = sv.p;
+        return r;
+    }
+    r.p = r.scratch = gaamd_dev_malloc((size_t)(hi - lo + 1) * v.elemsize);
+    if (!r.p) fatal("%s: no device memory for %ld elements of scratch", what, hi - lo + 1);
+    const long ld[1] = {0};
+    if (use == V_READ) patch_op(GA_GET, g_v, &lo, &hi, r.p, ld, nullptr);
+    return r;
+}
+
+// the kernel has written the scratch: store it into g_v, complete at its owner, and free it
+static void vec_done(int g_v, long lo, long hi, VecPart &r, VecUse use, const char *what) {
+    if (gaamd_sync(gaamd_stream()) != 0) fatal("%s: the stream failed", what);
+    if (!r.scratch) return;
+    if (use == V_WRITE) {
+        const long ld[1] = {0};
+        patch_op(GA_PUT, g_v, &lo, &hi, r.scratch, ld, nullptr);
+        comex_fence_all(COMEX_GROUP_WORLD);
+    }
+    gaamd_dev_free(r.scratch);
+    r.scratch = nullptr;
+}
+
+static void need_vector(const GArray &a, int g_v, long len, const char *what) {
+    const GArray &v = arr(g_v);
+    if (v.ndim != 1) fatal("%s: '%s' has rank %d, a vector of rank 1 is needed", what, v.name.c_str(), v.ndim);
+    if (v.type != a.type) fatal("%s: types of '%s' and '%s' differ", what, a.name.c_str(), v.name.c_str());
+    if (v.dims[0] != len) fatal("%s: '%s' has %ld elements, %ld are needed", what, v.name.c_str(), v.dims[0], len);
+    need_hbm(v, what);
+}
+
+static void diagonal_call(int fn, int g_a, int g_v, const void *c, const char *what) {
+    GArray &a = arr(g_a);
+    if (a.ndim != 2) fatal("%s: arrays of rank other than 2 are not supported", what);
+    need_hbm(a, what);
+    const VecUse use = fn == GAAMD_DIAG_GET ? V_WRITE : (fn == GAAMD_DIAG_SET || fn == GAAMD_DIAG_ADD) ? V_READ : V_NONE;
+    if (use != V_NONE) need_vector(a, g_v, std::min(a.dims[0], a.dims[1]), what);
+    if (fn == GAAMD_DIAG_SHIFT && !c) fatal("%s: the constant is missing", what);
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_stat.numdiag++;
+    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
+    whole(a, lo, hi);
+    const Sub s = own_sub(a, lo, hi);
+    // rows plo[1]..phi[1], columns plo[0]..phi[0]: the diagonal elements d0..d1 (1-based)
+    const long d0 = s.any ? std::max(s.plo[0], s.plo[1]) : 1, d1 = s.any ? std::min(s.phi[0], s.phi[1]) : 0;
+    if (d0 <= d1) {
+        const long n = d1 - d0 + 1;
+        char *p = s.p + ((d0 - s.plo[1]) * s.ext[0] + (d0 - s.plo[0])) * a.elemsize;
+        VecPart v;
+        if (use != V_NONE) v = vec_part(g_v, d0, d1, use, what);
+        const int rc = gaamd_diagonal(a.optype, fn, n, p, (long long)(s.ext[0] + 1) * a.elemsize, v.p, a.elemsize, c,
+                                      gaamd_stream());
+        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        vec_done(g_v, d0, d1, v, use, what);
+        g_stat.mathloc += (double)n * a.elemsize * (use == V_NONE && fn == GAAMD_DIAG_ZERO ? 1 : 2);
+    }
+    math_end(what);
+}
+
+static void scale_rc_call(bool rows, int g_a, int g_v, const char *what) {
+    GArray &a = arr(g_a);
+    if (a.ndim != 2) fatal("%s: arrays of rank other than 2 are not supported", what);
+    need_hbm(a, what);
+    // C subscript i (rows) is internal index 1, j (columns) internal index 0
+    const int dim = rows ? 1 : 0;
+    need_vector(a, g_v, a.dims[dim], what);
+    comex_barrier(COMEX_GROUP_WORLD);
+    (rows ? g_stat.numscalerows : g_stat.numscalecols)++;
+    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
+    whole(a, lo, hi);
+    const Sub s = own_sub(a, lo, hi);
+    if (s.any) {
+        VecPart v = vec_part(g_v, s.plo[dim], s.phi[dim], V_READ, what);
+        const int rc = rows ? gaamd_scale_rows(a.optype, s.count[1], s.count[0], s.p, s.ext[0], v.p, gaamd_stream())
+                            : gaamd_scale_cols(a.optype, s.count[1], s.count[0], s.p, s.ext[0], v.p, gaamd_stream());
+        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        vec_done(g_v, s.plo[dim], s.phi[dim], v, V_READ, what);
+        g_stat.mathloc += 2 * s.bytes;
+    }
+    math_end(what);
+}
+
+// pnga_norm1 / pnga_norm_infinity: each rank's norm of its block, then the gop in the element's
+// type ("+" / "max"); every rank returns the same bits
+static void norm_call(int kind, int g_a, double *nm, const char *what) {
+    GArray &a = arr(g_a);
+    if (a.ndim != 1 && a.ndim != 2) fatal("%s: arrays of rank other than 1 or 2 are not supported", what);
+    if (!nm) fatal("%s: the result is missing", what);
+    need_hbm(a, what);
+    comex_barrier(COMEX_GROUP_WORLD);
+    (kind == GAAMD_NORM_ONE ? g_stat.numnorm1 : g_stat.numnorminf)++;
+    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
+    whole(a, lo, hi);
+    const Sub s = own_sub(a, lo, hi);
+    union { int i; long l; float f; double d; } res;
+    memset(&res, 0, sizeof(res));   // a rank owning nothing contributes 0
+    if (s.any) {
+        const int rc = gaamd_patch_norm(a.optype, kind, s.p, s.stride, s.count, a.ndim, &res, gaamd_stream());
+        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        g_stat.mathloc += s.bytes;
+    }
+    char opname[4];
+    snprintf(opname, sizeof(opname), "%s", kind == GAAMD_NORM_ONE ? "+" : "max");
+    switch (a.type) {
+    case C_INT: armci_msg_igop(&res.i, 1, opname); *nm = (double)res.i; break;
+    case C_LONG: armci_msg_lgop(&res.l, 1, opname); *nm = (double)res.l; break;
+    case C_FLOAT:
+    case C_SCPL: armci_msg_fgop(&res.f, 1, opname); *nm = (double)res.f; break;
+    default: armci_msg_dgop(&res.d, 1, opname); *nm = res.d; break;
+    }
+    comex_barrier(COMEX_GROUP_WORLD);
+}
+
+void GA_Shift_diagonal(int g_a, void *c) { diagonal_call(GAAMD_DIAG_SHIFT, g_a, 0, c, "GA_Shift_diagonal"); }
+void GA_Set_diagonal(int g_a, int g_v) { diagonal_call(GAAMD_DIAG_SET, g_a, g_v, nullptr, "GA_Set_diagonal"); }
+void GA_Zero_diagonal(int g_a) { diagonal_call(GAAMD_DIAG_ZERO, g_a, 0, nullptr, "GA_Zero_diagonal"); }
+void GA_Add_diagonal(int g_a, int g_v) { diagonal_call(GAAMD_DIAG_ADD, g_a, g_v, nullptr, "GA_Add_diagonal"); }
+void GA_Get_diag(int g_a, int g_v) { diagonal_call(GAAMD_DIAG_GET, g_a, g_v, nullptr, "GA_Get_diag"); }
+void GA_Scale_rows(int g_a, int g_v) { scale_rc_call(true, g_a, g_v, "GA_Scale_rows"); }
+void GA_Scale_cols(int g_a, int g_v) { scale_rc_call(false, g_a, g_v, "GA_Scale_cols"); }
+void GA_Norm1(int g_a, double *nm) { norm_call(GAAMD_NORM_ONE, g_a, nm, "GA_Norm1"); }
+void GA_Norm_infinity(int g_a, double *nm) { norm_call(GAAMD_NORM_INF, g_a, nm, "GA_Norm_infinity"); }
+
 void GA_Print_stats(void) {
     printf("[%d] GA on-device calls: fill %ld, scale %ld, add %ld, copy %ld, dot %ld; local bytes moved %.0f; "
            "gemm %ld\n",
@@ -1708,6 +1851,8 @@ void GA_Print_stats(void) {
            my_rank(), g_stat.numelem[GAAMD_ELEM_ABS], g_stat.numelem[GAAMD_ELEM_ADD_CONST],
            g_stat.numelem[GAAMD_ELEM_RECIP], g_stat.numelem[GAAMD_ELEM_MUL], g_stat.numelem[GAAMD_ELEM_DIV],
            g_stat.numelem[GAAMD_ELEM_MAX], g_stat.numelem[GAAMD_ELEM_MIN], g_stat.numselect);
+    printf("[%d] GA matrix calls: diagonal %ld, scale_rows %ld, scale_cols %ld, norm1 %ld, norm_infinity %ld\n",
+           my_rank(), g_stat.numdiag, g_stat.numscalerows, g_stat.numscalecols, g_stat.numnorm1, g_stat.numnorminf);
 }
 
 }  // extern "C"

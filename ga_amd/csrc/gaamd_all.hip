@@ -9,5 +9,6 @@
 #include "gaamd_misc.hip"
 #include "gaamd_patch.hip"
 #include "gaamd_select.hip"
+#include "gaamd_matrix.hip"
 #include "gaamd_gemm.hip"
 #include "gaamd_transpose.hip"

@@ -147,6 +147,20 @@ int launch_patch_elem2(int op, int fn, const void *a, const long long *a_stride,
 // `stream`; value, key (may be null) and index are host memory.  1 and *index = -1 on a count of zero.
 int launch_patch_select(int op, int want_max, const void *a, const long long *a_stride, const long long *count,
                         int ndim, void *value, void *key, long long *index, hipStream_t stream);
+// ---- GA's matrix.c calls (gaamd_matrix.hip; ga_amd.h gaamd_patch_norm / _diagonal / _scale_rows / _cols) ----
+// the 1-norm (sum of |x|) or infinity norm (max of |x|) of a patch; launch_patch_dot's geometry,
+// checks and codes; synchronises `stream`; result (host): one value of the element's type, for
+// complex of its real type
+enum { kNormOne = 1, kNormInf = 2 };
+int launch_patch_norm(int op, int kind, const void *a, const long long *a_stride, const long long *count, int ndim,
+                      void *result, hipStream_t stream);
+// n elements, element i of the matrix side at a + i * a_step bytes, of the vector side at v + i * v_step
+enum { kDiagGet = 1, kDiagSet = 2, kDiagAdd = 3, kDiagShift = 4, kDiagZero = 5 };
+int launch_diagonal(int op, int fn, long long n, void *a, long long a_step, void *v, long long v_step,
+                    const void *scalar, hipStream_t stream);
+// a[i][j] *= v[i] (cols: v[j]) on a row-major rows x ncols matrix, lda in elements; complex part by part
+int launch_scale_rc(int op, bool cols, long long rows, long long ncols, void *a, long long lda, const void *v,
+                    hipStream_t stream);
 struct PatchPlan;
 // launch_patch_add's checks without a launch (no device): 0 launch, 1 nothing to do, < 0 error;
 // plan[0..3] = {vector width, row levels after merging, rows, vectors per row}

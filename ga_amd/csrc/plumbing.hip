@@ -117,6 +117,24 @@ int gaamd_patch_select(int op, int want_max, const void *a, const long long *a_s
     return launch_patch_select(op, want_max, a, a_stride, count, ndim, value, key, index, stream_of(stream));
 }
 
+int gaamd_patch_norm(int op, int kind, const void *a, const long long *a_stride, const long long *count, int ndim,
+                     void *result, void *stream) {
+    return launch_patch_norm(op, kind, a, a_stride, count, ndim, result, stream_of(stream));
+}
+
+int gaamd_diagonal(int op, int fn, long long n, void *a, long long a_step, void *v, long long v_step,
+                   const void *scalar, void *stream) {
+    return launch_diagonal(op, fn, n, a, a_step, v, v_step, scalar, stream_of(stream));
+}
+
+int gaamd_scale_rows(int op, long long rows, long long cols, void *a, long long lda, const void *v, void *stream) {
+    return launch_scale_rc(op, false, rows, cols, a, lda, v, stream_of(stream));
+}
+
+int gaamd_scale_cols(int op, long long rows, long long cols, void *a, long long lda, const void *v, void *stream) {
+    return launch_scale_rc(op, true, rows, cols, a, lda, v, stream_of(stream));
+}
+
 int gaamd_gemm(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
                const void *a, long long lda, const void *b, long long ldb, const void *beta, void *c, long long ldc,
                void *stream) {

@@ -221,6 +221,49 @@ void GA_Elem_divide_patch(int g_a, int *alo, int *ahi, int g_b, int *blo, int *b
 void GA_Elem_maximum_patch(int g_a, int *alo, int *ahi, int g_b, int *blo, int *bhi, int g_c, int *clo, int *chi);
 void GA_Elem_minimum_patch(int g_a, int *alo, int *ahi, int g_b, int *blo, int *bhi, int g_c, int *clo, int *chi);
 void NGA_Select_elem(int g_a, char *op, void *val, int *index);
+/* Diagonals, row / column scaling and norms on HBM blocks (capi.c:4940-4986 -> global/src/matrix.c).
+   Collective, GA_Sync on entry and exit; the reference's arithmetic expression for expression
+   (ga_amd.h gaamd_diagonal / gaamd_scale_rows / gaamd_scale_cols / gaamd_patch_norm).  All six types.
+     GA_Shift_diagonal(g_a, c)   a[i][i] += *c          GA_Zero_diagonal(g_a)   a[i][i] = 0
+     GA_Set_diagonal(g_a, g_v)   a[i][i] = v[i]         GA_Add_diagonal(g_a, g_v)   a[i][i] += v[i]
+     GA_Get_diag(g_a, g_v)       v[i] = a[i][i]
+   g_a has rank 2, g_v rank 1 and min(dims[0], dims[1]) elements (matrix.c:1512).  Complex adds
+   work on the real and the imaginary part each.
+     GA_Scale_rows(g_a, g_v)     a[i][j] *= v[i],  v of dims[0] elements
+     GA_Scale_cols(g_a, g_v)     a[i][j] *= v[j],  v of dims[1] elements
+   SUBSCRIPTS ARE THE C API's: i is the first C subscript of g_a, j the second, and dims[] is what
+   NGA_Create was called with.  (capi.c reverses the index order and therefore hands
+   GA_Scale_rows to the Fortran-order pnga_scale_cols and the reverse; the result is the above.)
+   Complex scaling is PART BY PART, re *= v.re and im *= v.im (matrix.c:2494-2503, 2700-2710):
+   the reference's expression, not a complex product.
+   Owner of g_a computes: a rank cuts the diagonal by its own block (rows r0..r1, columns
+   c0..c1: elements max(r0,c0)..min(r1,c1)), or takes the rows / columns of its block.  Where that
+   range of g_v lies wholly in the rank's own block of g_v it is used in place; otherwise it is
+   fetched into HBM scratch with NGA_Get's path (GA_Get_diag: written to scratch by the kernel,
+   then stored with NGA_Put's path, complete at its owner before the closing sync).  The scratch
+   is freed before return.  REGULAR or irregular block maps, which need not agree between g_a
+   and g_v.  A rank that owns nothing of the diagonal launches nothing and takes part in the syncs.
+     GA_Norm1(g_a, nm)          *nm = sum |a|     GA_Norm_infinity(g_a, nm)   *nm = max |a|
+   over ALL elements of an array of rank 1 or 2, as matrix.c:998-1018 / 1306-1325 compute them
+   (not the induced matrix norms); |x| is GA_ABS, for complex sqrt(re*re + im*im).  Each rank
+   reduces its block in the element's own type (complex: its real type; integers wrap), a rank
+   owning nothing contributes 0, the ranks combine with armci_msg_?gop "+" / "max" in that type,
+   and *nm is that value converted to double.  Every rank returns the same bits and the same
+   arrays give the same bits on every call.  GA_Norm_infinity also returns the same bits on any
+   number of ranks and any block map; GA_Norm1 does so for the integer types only -- for the
+   floating-point types its roundings depend on how the array is cut, as the dot products' do.
+   Aborts through GA_Error, before the first sync or launch: g_a not of rank 2 (diagonal and
+   scale calls) or not of rank 1 or 2 (norms), g_v not of rank 1 or of the wrong length, types
+   that differ, a missing c or nm, an array in a host segment. */
+void GA_Shift_diagonal(int g_a, void *c);
+void GA_Set_diagonal(int g_a, int g_v);
+void GA_Zero_diagonal(int g_a);
+void GA_Add_diagonal(int g_a, int g_v);
+void GA_Get_diag(int g_a, int g_v);
+void GA_Scale_rows(int g_a, int g_v);
+void GA_Scale_cols(int g_a, int g_v);
+void GA_Norm1(int g_a, double *nm);
+void GA_Norm_infinity(int g_a, double *nm);
 /* global arrays alive on this rank (temporaries of the general path are destroyed
    before their call returns) */
 int gaamd_ga_live_arrays(void);

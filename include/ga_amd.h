@@ -146,6 +146,71 @@ int gaamd_patch_select(int op, int want_max, const void *a, const long long *a_s
                        const long long *count, int ndim, void *value /* host, one element */,
                        void *key /* host, may be NULL: the compared quantity */,
                        long long *index /* host */, void *stream);
+/* The kernels under GA's matrix.c calls (ga.h: GA_Norm1 / GA_Norm_infinity, the diagonal calls,
+ * GA_Scale_rows / GA_Scale_cols), global/src/matrix.c expression for expression, no FMA, all six
+ * types, integers in unsigned (wraparound) arithmetic, every offset 64-bit.
+ *
+ * gaamd_patch_norm: a one-operand reduction over a patch with gaamd_patch_dot's geometry, checks
+ * and negative codes (-4 also for an unknown kind, -5 a missing result).  The per-element
+ * quantity q is GA_ABS(x) = x >= 0 ? x : -x for the real and integer types (INT_MIN / LONG_MIN
+ * wrap to themselves, -0.0 stays -0.0) and sqrt(re*re + im*im) for the complex ones: two
+ * products and one sum in the real type, then the correctly rounded square root (for C_SCPL the
+ * float one; the reference's (float)sqrt((double)x) is the same number).
+ *   GAAMD_NORM_ONE  the sum of q in the element's own type (complex: its real type; integers wrap),
+ *                   matrix.c:1118-1171.  The reduction has gaamd_patch_dot's fixed shape -- lane,
+ *                   wave tree, waves in order, one partial per workgroup, one final workgroup, no
+ *                   atomics -- so the same input gives the same bits on every run.
+ *   GAAMD_NORM_INF  the maximum of q, matrix.c:801-859.  It does not depend on the order it is
+ *                   taken in, so it is exact on any grid.  Signed zeros: -0.0 only if every q is
+ *                   -0.0, else +0.0 before -0.0.  Integers compare signed, so a wrapped INT_MIN
+ *                   loses to every other value.  A patch holding a NaN gives an unspecified
+ *                   result, as for gaamd_patch_select.
+ * It synchronises its stream and writes `result` (host): one value of the element's type, for
+ * complex of its real type.  A count of zero: 0, the type's zero written, nothing launched.
+ *
+ * gaamd_diagonal: n elements, element i of the matrix side at a + i * a_step BYTES and of the
+ * vector side at v + i * v_step bytes (for the diagonal of a row-major matrix a_step =
+ * (ld + 1) * elemsize; steps may be negative).  One lane per element; a 16-byte element moves
+ * as one 16-byte access where bases and steps are 16-byte aligned, an 8-byte complex one as one
+ * 8-byte access where they are 8-byte aligned, and as its parts otherwise.  Returns with the
+ * kernel in flight.
+ *   GAAMD_DIAG_GET    v_i = a_i, a bit copy (NaN payloads and -0.0 survive)
+ *   GAAMD_DIAG_SET    a_i = v_i, a bit copy
+ *   GAAMD_DIAG_ADD    a_i += v_i, complex real and imaginary part each      matrix.c:1640-1690
+ *   GAAMD_DIAG_SHIFT  a_i += *scalar, complex part by part (v is not used)  2080-2127
+ *   GAAMD_DIAG_ZERO   a_i = 0 (v is not used)
+ * Negative codes, all before any launch: -4 an unknown op or fn, -3 a negative n, -7 n of 2^39 or
+ * more, -5 a missing a, a missing scalar for SHIFT or a missing v for GET / SET / ADD, -8 a base
+ * or step below 4-byte alignment, -11 the byte spans of the a side and the v side (first element
+ * to last) overlap.  n == 0: 0, nothing launched.
+ * (The name gaamd_diag is the library's diagnostic entry point, last section.)
+ *
+ * gaamd_scale_rows: a[i][j] *= v[i];  gaamd_scale_cols: a[i][j] *= v[j];  i < rows, j < cols, in
+ * place on a row-major matrix with lda in ELEMENTS between rows; v is contiguous (rows, resp.
+ * cols elements).  Real types: one product.  Complex is PART BY PART, re *= v.re and im *= v.im
+ * (matrix.c:2494-2503, 2700-2710): the reference's expression, NOT a complex product.  On the
+ * map kernel's streaming shape: 16-byte vectors where the base, lda, the row length (and for
+ * cols v's base) allow, 8 or 4 bytes otherwise; non-temporal accesses to a; more than 65535 rows
+ * in several launches.  rows: the multiplier is uniform per workgroup; cols: v's vector is
+ * loaded beside a's with a cached load (every row reads it again).  Nothing outside the rows x
+ * cols elements is written.  Return with the kernel in flight.  Codes as gaamd_patch_scale:
+ * -3 a negative extent, -4 an unknown op, -5 v missing, -6 lda below cols, -7 2^31 rows or more,
+ * -8 a base below 4-byte alignment, and -11 v's bytes overlap a's span (first stored element to
+ * last).  A zero extent: 0, no launch. */
+#define GAAMD_NORM_ONE 1
+#define GAAMD_NORM_INF 2
+#define GAAMD_DIAG_GET 1
+#define GAAMD_DIAG_SET 2
+#define GAAMD_DIAG_ADD 3
+#define GAAMD_DIAG_SHIFT 4
+#define GAAMD_DIAG_ZERO 5
+int gaamd_patch_norm(int op, int kind, const void *a, const long long *a_stride,
+                     const long long *count, int ndim,
+                     void *result /* host, one value of the element's (complex: real) type */, void *stream);
+int gaamd_diagonal(int op, int fn, long long n, void *a, long long a_step, void *v, long long v_step,
+                   const void *scalar /* SHIFT only */, void *stream);
+int gaamd_scale_rows(int op, long long rows, long long cols, void *a, long long lda, const void *v, void *stream);
+int gaamd_scale_cols(int op, long long rows, long long cols, void *a, long long lda, const void *v, void *stream);
 /* Row-major GEMM on the gfx950 matrix cores, for op = COMEX_ACC_DBL (v_mfma_f64_16x16x4_f64)
  * and COMEX_ACC_FLT (v_mfma_f32_16x16x4_f32); the kernel under GA_Dgemm / GA_Sgemm (ga.h):
  *   C[i][j] = alpha * sum_k op(A)[i][k] * op(B)[k][j] + beta * C[i][j],  i < m, j < n, kk < k
