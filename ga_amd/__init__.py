@@ -250,6 +250,67 @@ def scale_cols(op, rows, cols, a, lda, v, stream=None):
     return lib().gaamd_scale_cols(op, rows, cols, ctypes.c_void_p(a), lda, ctypes.c_void_p(v) if v else None, stream)
 
 
+# GA's sparse.c calls at kernel level (gaamd_enum / _scan_tail / _scan / _mask_count / _mask_pack /
+# _mask_unpack): contiguous 1-D device arrays, n in elements, op the value type and mop the mask
+# type; the return code is handed back (0, or the negative codes of ga_amd.h).  The compaction's
+# wrappers are mask_pack / mask_unpack: pack and unpack are the strided ones above.
+GAAMD_SCAN_COPY, GAAMD_SCAN_ADD, GAAMD_SCAN_ADD_EXCL = 1, 2, 3
+
+
+def _vp(a):
+    return ctypes.c_void_p(a) if a else None
+
+
+def scan_tile(op, mop):
+    """elements per tile (workgroup) of the scan and compaction kernels"""
+    return lib().gaamd_scan_tile(op, mop)
+
+
+def scan_agg_span():
+    """tile aggregates the aggregate scan's one workgroup takes per pass of its loop"""
+    return lib().gaamd_scan_agg_span()
+
+
+def enum(op, n, first, start, stride, dst, stream=None):
+    """dst[i] = start + (T)(first + i) * stride; start / stride of None reach the library as NULL"""
+    ka, ap = scale_buffer(op, start) if start is not None else (None, None)
+    kb, bp = scale_buffer(op, stride) if stride is not None else (None, None)
+    return lib().gaamd_enum(op, n, first, ap, bp, _vp(dst), stream)
+
+
+def scan_tail(op, fn, mop, n, src, msk, stream=None):
+    """(return code, has_flag, the open value at the end of the range as a one-element array)"""
+    tail = np.zeros(1, dtype=OP_DTYPE.get(op, np.complex128))
+    tail.view(np.uint8)[:] = 0xA5   # the call has to write it, the zero of n == 0 too
+    flag = ctypes.c_int(-1)
+    rc = lib().gaamd_scan_tail(op, fn, mop, n, _vp(src), _vp(msk), ctypes.byref(flag),
+                               tail.ctypes.data_as(ctypes.c_void_p), stream)
+    return rc, flag.value, tail
+
+
+def scan(op, fn, mop, n, src, msk, dst, open=0, carry=None, stream=None):
+    """the segmented scan; carry: the open segment's value so far (with open != 0)"""
+    kc, cp = scale_buffer(op, carry) if carry is not None else (None, None)
+    return lib().gaamd_scan(op, fn, mop, n, _vp(src), _vp(msk), _vp(dst), int(open), cp, stream)
+
+
+def mask_count(mop, n, msk, stream=None):
+    """(return code, the number of set elements)"""
+    cnt = ctypes.c_longlong(-1)
+    rc = lib().gaamd_mask_count(mop, n, _vp(msk), ctypes.byref(cnt), stream)
+    return rc, cnt.value
+
+
+def mask_pack(op, mop, n, src, msk, packed, stream=None):
+    """packed[k] = src[f_k], f_k the k-th set element of msk"""
+    return lib().gaamd_mask_pack(op, mop, n, _vp(src), _vp(msk), _vp(packed), stream)
+
+
+def mask_unpack(op, mop, n, packed, msk, dst, stream=None):
+    """dst[f_k] = packed[k]; the other elements of dst are not written"""
+    return lib().gaamd_mask_unpack(op, mop, n, _vp(packed), _vp(msk), _vp(dst), stream)
+
+
 def patch_add_plan(op, a, a_stride, b, b_stride, c, c_stride, count):
     """gaamd_patch_add's checks without a launch (no GPU): (code, {width, levels, rows, nvec})"""
     out = (ctypes.c_longlong * 4)()

@@ -91,6 +91,7 @@ static struct {
     long numelem[8] = {0};   // by GAAMD_ELEM_* code
     long numselect = 0;
     long numdiag = 0, numscalerows = 0, numscalecols = 0, numnorm1 = 0, numnorminf = 0;
+    long numenum = 0, numscancopy = 0, numscanadd = 0, numpack = 0, numunpack = 0;
     double mathloc = 0;
 } g_stat;
 
@@ -1836,6 +1837,197 @@ void GA_Scale_cols(int g_a, int g_v) { scale_rc_call(false, g_a, g_v, "GA_Scale_
 void GA_Norm1(int g_a, double *nm) { norm_call(GAAMD_NORM_ONE, g_a, nm, "GA_Norm1"); }
 void GA_Norm_infinity(int g_a, double *nm) { norm_call(GAAMD_NORM_INF, g_a, nm, "GA_Norm_infinity"); }
 
+// ---- enumerate, segmented scans, pack / unpack (global/src/sparse.c) ------------------------
+// 1-D arrays.  Each rank runs the kernels of ga_amd.h (gaamd_enum, gaamd_scan_tail / gaamd_scan,
+// gaamd_mask_count / gaamd_mask_pack / gaamd_mask_unpack) on its part of [lo, hi] where it lies;
+// what crosses ranks is one small host exchange per call.  For a 1-D array rank r owns block r,
+// so rank order is block order.
+static void need_1d(const GArray &a, const char *what) {
+    if (a.ndim != 1) fatal("%s: '%s' has rank %d, applicable to 1-dim arrays", what, a.name.c_str(), a.ndim);
+    need_hbm(a, what);
+}
+
+static void need_range(const GArray &a, long lo, long hi, const char *what) {
+    if (lo > hi || lo < 1 || hi > a.dims[0])
+        fatal("%s: range [%ld, %ld] outside '%s' of %ld elements", what, lo - 1, hi - 1, a.name.c_str(), a.dims[0]);
+}
+
+// one slot of `per` longs per rank in a zeroed array, combined with the integer "+" gop: every
+// slot has one writer, so the bits arrive as they were (x + 0), as sparse.c does with lim[]
+static void exchange_slots(std::vector<long> &slots) {
+    char op[2] = "+";
+    armci_msg_lgop(slots.data(), (int)slots.size(), op);
+}
+
+// a = a + b in the array's type on the host: complex part by part, integers unsigned
+static void host_add(int type, void *a, const void *b) {
+    switch (type) {
+    case C_INT: { uint32_t x, y; memcpy(&x, a, 4); memcpy(&y, b, 4); x += y; memcpy(a, &x, 4); break; }
+    case C_LONG: { uint64_t x, y; memcpy(&x, a, 8); memcpy(&y, b, 8); x += y; memcpy(a, &x, 8); break; }
+    case C_FLOAT:
+    case C_SCPL: {
+        float x[2], y[2];
+        const int np = type == C_SCPL ? 2 : 1;
+        memcpy(x, a, 4 * np); memcpy(y, b, 4 * np);
+        for (int k = 0; k < np; k++) x[k] = x[k] + y[k];
+        memcpy(a, x, 4 * np);
+        break;
+    }
+    default: {
+        double x[2], y[2];
+        const int np = type == C_DCPL ? 2 : 1;
+        memcpy(x, a, 8 * np); memcpy(y, b, 8 * np);
+        for (int k = 0; k < np; k++) x[k] = x[k] + y[k];
+        memcpy(a, x, 8 * np);
+        break;
+    }
+    }
+}
+
+static void enum_call(int g_a, long lo, long hi, const void *start, const void *inc) {
+    const char *what = "GA_Patch_enum";
+    GArray &a = arr(g_a);
+    need_1d(a, what);
+    need_range(a, lo, hi, what);
+    if (!start || !inc) fatal("%s: the start or the increment is missing", what);
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_stat.numenum++;
+    const Sub s = own_sub(a, &lo, &hi);
+    if (s.any) {
+        const int rc = gaamd_enum(a.optype, s.count[0], s.plo[0] - lo, start, inc, s.p, gaamd_stream());
+        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        g_stat.mathloc += s.bytes;
+    }
+    math_end(what);
+}
+
+static void scan_call(int fn, int g_src, int g_dst, int g_msk, long lo, long hi, const char *what) {
+    GArray &src = arr(g_src), &dst = arr(g_dst), &msk = arr(g_msk);
+    need_1d(src, what);
+    need_1d(dst, what);
+    need_1d(msk, what);
+    if (g_src == g_dst) fatal("%s: src and dst must be different arrays", what);
+    if (src.type != dst.type) fatal("%s: src and dst arrays must be same type", what);
+    if (!same_distr(src, msk)) fatal("%s: different distribution src", what);
+    if (!same_distr(dst, msk)) fatal("%s: different distribution dst", what);
+    need_range(msk, lo, hi, what);
+    comex_barrier(COMEX_GROUP_WORLD);
+    (fn == GAAMD_SCAN_COPY ? g_stat.numscancopy : g_stat.numscanadd)++;
+    const int me = my_rank(), np = world_size();
+    const Sub ss = own_sub(src, &lo, &hi), sd = own_sub(dst, &lo, &hi), sm = own_sub(msk, &lo, &hi);
+    // slot r: {1 rank r has a part of the range | 2 it holds a set element, its tail (16 bytes)}
+    std::vector<long> slots((size_t)np * 3, 0);
+    if (sm.any) {
+        int flag = 0;
+        long tail[2] = {0, 0};
+        const int rc = gaamd_scan_tail(src.optype, fn, msk.optype, sm.count[0], ss.p, sm.p, &flag, tail, gaamd_stream());
+        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        slots[(size_t)me * 3] = 1 | (flag ? 2 : 0);
+        slots[(size_t)me * 3 + 1] = tail[0];
+        slots[(size_t)me * 3 + 2] = tail[1];
+    }
+    exchange_slots(slots);
+    if (sm.any) {
+        // the carry: the tail of the nearest rank before this one that holds a set element, plus
+        // (ADD) the tails of the ranks between, in ascending order
+        int from = me - 1;
+        while (from >= 0 && !(slots[(size_t)from * 3] & 2)) from--;
+        long carry[2] = {0, 0};
+        if (from >= 0) {
+            memcpy(carry, &slots[(size_t)from * 3 + 1], 16);
+            if (fn != GAAMD_SCAN_COPY)
+                for (int r = from + 1; r < me; r++)
+                    if (slots[(size_t)r * 3] & 1) host_add(src.type, carry, &slots[(size_t)r * 3 + 1]);
+        }
+        const int rc = gaamd_scan(src.optype, fn, msk.optype, sm.count[0], ss.p, sm.p, sd.p, from >= 0 ? 1 : 0, carry,
+                                  gaamd_stream());
+        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        g_stat.mathloc += 3 * ss.bytes + 2 * sm.bytes;   // src twice and dst, msk twice
+    }
+    math_end(what);
+}
+
+// the packed side: elements [place + 1, place + cnt] (1-based) of g_b for this rank's kernel.
+// The kernel judges overlap with `packed` at n elements, so the rank's own block is used in
+// place only where n elements from there stay inside it; otherwise scratch of n elements.
+static VecPart packed_part(int g_b, long place, long cnt, long n, bool read, const char *what) {
+    VecPart r;
+    GArray &b = arr(g_b);
+    long lo = place + 1, hi = place + cnt, blo[GA_MAX_DIM], bhi[GA_MAX_DIM];
+    if (block_elems(b, my_rank(), blo, bhi) > 0 && blo[0] <= lo && lo + n - 1 <= bhi[0]) {
+        r.p = (char *)b.ptr[my_rank()] + (lo - blo[0]) * b.elemsize;
+        return r;
+    }
+    r.p = r.scratch = gaamd_dev_malloc((size_t)n * b.elemsize);
+    if (!r.p) fatal("%s: no device memory for %ld elements of scratch", what, n);
+    const long ld[1] = {0};
+    if (read) patch_op(GA_GET, g_b, &lo, &hi, r.p, ld, nullptr);
+    return r;
+}
+
+static void pack_call(bool unpack, int g_src, int g_dst, int g_msk, long lo, long hi, int *icount) {
+    const char *what = unpack ? "GA_Unpack" : "GA_Pack";
+    GArray &src = arr(g_src), &dst = arr(g_dst), &msk = arr(g_msk);
+    need_1d(src, what);
+    need_1d(dst, what);
+    need_1d(msk, what);
+    if (g_src == g_dst) fatal("%s: src and dst must be different arrays", what);
+    if (src.type != dst.type) fatal("%s: src and dst must be same type", what);
+    // `full` lies beside the mask element for element, `thin` is the packed side (any block map)
+    const int g_full = unpack ? g_dst : g_src, g_thin = unpack ? g_src : g_dst;
+    GArray &full = arr(g_full), &thin = arr(g_thin);
+    if (!same_distr(full, msk)) fatal("%s: %s and msk distributions differ", what, unpack ? "dst" : "src");
+    need_range(msk, lo, hi, what);
+    if (!icount) fatal("%s: icount is missing", what);
+    comex_barrier(COMEX_GROUP_WORLD);
+    (unpack ? g_stat.numunpack : g_stat.numpack)++;
+    const int me = my_rank(), np = world_size();
+    const Sub sf = own_sub(full, &lo, &hi), sm = own_sub(msk, &lo, &hi);
+    std::vector<long> counts((size_t)np, 0);
+    if (sm.any) {
+        long long c = 0;
+        const int rc = gaamd_mask_count(msk.optype, sm.count[0], sm.p, &c, gaamd_stream());
+        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        counts[(size_t)me] = (long)c;
+    }
+    exchange_slots(counts);
+    long place = 0, total = 0;
+    for (int r = 0; r < np; r++) {
+        if (r < me) place += counts[(size_t)r];
+        total += counts[(size_t)r];
+    }
+    *icount = (int)total;
+    if (total > thin.dims[0])   // every rank knows the total: all end here, nothing was moved
+        fatal("%s: %ld set elements do not fit the packed array '%s' of %ld elements", what, total, thin.name.c_str(),
+              thin.dims[0]);
+    const long cnt = counts[(size_t)me];
+    if (cnt > 0) {
+        const long n = sm.count[0];
+        VecPart v = packed_part(g_thin, place, cnt, n, unpack, what);
+        const int rc = unpack ? gaamd_mask_unpack(full.optype, msk.optype, n, v.p, sm.p, sf.p, gaamd_stream())
+                              : gaamd_mask_pack(full.optype, msk.optype, n, sf.p, sm.p, v.p, gaamd_stream());
+        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        vec_done(g_thin, place + 1, place + cnt, v, unpack ? V_READ : V_WRITE, what);
+        g_stat.mathloc += 3.0 * sm.bytes + 2.0 * cnt * full.elemsize;   // msk three times, cnt elements in and out
+    }
+    math_end(what);
+}
+
+// capi.c:2261-2373: C subscripts, inclusive
+void GA_Patch_enum(int g_a, int lo, int hi, void *start, void *inc) { enum_call(g_a, (long)lo + 1, (long)hi + 1, start, inc); }
+void GA_Scan_copy(int g_src, int g_dst, int g_msk, int lo, int hi) {
+    scan_call(GAAMD_SCAN_COPY, g_src, g_dst, g_msk, (long)lo + 1, (long)hi + 1, "GA_Scan_copy");
+}
+void GA_Scan_add(int g_src, int g_dst, int g_msk, int lo, int hi, int excl) {
+    scan_call(excl ? GAAMD_SCAN_ADD_EXCL : GAAMD_SCAN_ADD, g_src, g_dst, g_msk, (long)lo + 1, (long)hi + 1, "GA_Scan_add");
+}
+void GA_Pack(int g_src, int g_dst, int g_msk, int lo, int hi, int *icount) {
+    pack_call(false, g_src, g_dst, g_msk, (long)lo + 1, (long)hi + 1, icount);
+}
+void GA_Unpack(int g_src, int g_dst, int g_msk, int lo, int hi, int *icount) {
+    pack_call(true, g_src, g_dst, g_msk, (long)lo + 1, (long)hi + 1, icount);
+}
+
 void GA_Print_stats(void) {
     printf("[%d] GA on-device calls: fill %ld, scale %ld, add %ld, copy %ld, dot %ld; local bytes moved %.0f; "
            "gemm %ld\n",
@@ -1853,6 +2045,8 @@ void GA_Print_stats(void) {
            g_stat.numelem[GAAMD_ELEM_MAX], g_stat.numelem[GAAMD_ELEM_MIN], g_stat.numselect);
     printf("[%d] GA matrix calls: diagonal %ld, scale_rows %ld, scale_cols %ld, norm1 %ld, norm_infinity %ld\n",
            my_rank(), g_stat.numdiag, g_stat.numscalerows, g_stat.numscalecols, g_stat.numnorm1, g_stat.numnorminf);
+    printf("[%d] GA sparse calls: enum %ld, scan_copy %ld, scan_add %ld, pack %ld, unpack %ld\n", my_rank(),
+           g_stat.numenum, g_stat.numscancopy, g_stat.numscanadd, g_stat.numpack, g_stat.numunpack);
 }
 
 }  // extern "C"

@@ -10,5 +10,6 @@
 #include "gaamd_patch.hip"
 #include "gaamd_select.hip"
 #include "gaamd_matrix.hip"
+#include "gaamd_scan.hip"
 #include "gaamd_gemm.hip"
 #include "gaamd_transpose.hip"

@@ -161,6 +161,23 @@ int launch_diagonal(int op, int fn, long long n, void *a, long long a_step, void
 // a[i][j] *= v[i] (cols: v[j]) on a row-major rows x ncols matrix, lda in elements; complex part by part
 int launch_scale_rc(int op, bool cols, long long rows, long long ncols, void *a, long long lda, const void *v,
                     hipStream_t stream);
+// ---- GA's sparse.c calls (gaamd_scan.hip; ga_amd.h gaamd_enum / _scan_tail / _scan / _mask_count / _mask_pack /
+// _mask_unpack): contiguous 1-D arrays, n in elements, op the value type and mop the mask type (any two
+// COMEX_ACC_* types); the codes are the patch codes above (kPatchErrRange: n above 2^34) ----
+enum { kScanCopy = 1, kScanAdd = 2, kScanAddExcl = 3 };
+int scan_tile(int op, int mop);   // elements per tile (workgroup), or kPatchErrOp
+int scan_agg_span();              // tile aggregates per pass of the aggregate scan's loop
+int launch_enum(int op, long long n, long long first, const void *start, const void *stride, void *dst,
+                hipStream_t stream);
+// synchronises `stream`; has_flag and tail (one element) are host memory
+int launch_scan_tail(int op, int fn, int mop, long long n, const void *src, const void *msk, int *has_flag, void *tail,
+                     hipStream_t stream);
+int launch_scan(int op, int fn, int mop, long long n, const void *src, const void *msk, void *dst, int open,
+                const void *carry, hipStream_t stream);
+int launch_mask_count(int mop, long long n, const void *msk, long long *count, hipStream_t stream);   // synchronises
+// pack (unpack == false): arr = src, other = packed (written); unpack: arr = dst (written), other = packed
+int launch_mask_move(bool unpack, int op, int mop, long long n, const void *arr, const void *msk, const void *other,
+                     hipStream_t stream);
 struct PatchPlan;
 // launch_patch_add's checks without a launch (no device): 0 launch, 1 nothing to do, < 0 error;
 // plan[0..3] = {vector width, row levels after merging, rows, vectors per row}

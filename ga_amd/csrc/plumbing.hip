@@ -135,6 +135,36 @@ int gaamd_scale_cols(int op, long long rows, long long cols, void *a, long long 
     return launch_scale_rc(op, true, rows, cols, a, lda, v, stream_of(stream));
 }
 
+int gaamd_scan_tile(int op, int mop) { return scan_tile(op, mop); }
+
+int gaamd_scan_agg_span(void) { return scan_agg_span(); }
+
+int gaamd_enum(int op, long long n, long long first, const void *start, const void *stride, void *dst, void *stream) {
+    return launch_enum(op, n, first, start, stride, dst, stream_of(stream));
+}
+
+int gaamd_scan_tail(int op, int fn, int mop, long long n, const void *src, const void *msk, int *has_flag, void *tail,
+                    void *stream) {
+    return launch_scan_tail(op, fn, mop, n, src, msk, has_flag, tail, stream_of(stream));
+}
+
+int gaamd_scan(int op, int fn, int mop, long long n, const void *src, const void *msk, void *dst, int open,
+               const void *carry, void *stream) {
+    return launch_scan(op, fn, mop, n, src, msk, dst, open, carry, stream_of(stream));
+}
+
+int gaamd_mask_count(int mop, long long n, const void *msk, long long *count, void *stream) {
+    return launch_mask_count(mop, n, msk, count, stream_of(stream));
+}
+
+int gaamd_mask_pack(int op, int mop, long long n, const void *src, const void *msk, void *packed, void *stream) {
+    return launch_mask_move(false, op, mop, n, src, msk, packed, stream_of(stream));
+}
+
+int gaamd_mask_unpack(int op, int mop, long long n, const void *packed, const void *msk, void *dst, void *stream) {
+    return launch_mask_move(true, op, mop, n, dst, msk, packed, stream_of(stream));
+}
+
 int gaamd_gemm(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
                const void *a, long long lda, const void *b, long long ldb, const void *beta, void *c, long long ldc,
                void *stream) {

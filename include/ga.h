@@ -264,6 +264,54 @@ void GA_Scale_rows(int g_a, int g_v);
 void GA_Scale_cols(int g_a, int g_v);
 void GA_Norm1(int g_a, double *nm);
 void GA_Norm_infinity(int g_a, double *nm);
+/* Enumerate, segmented scans, pack and unpack on HBM blocks (capi.c:2261-2373 -> global/src/sparse.c):
+   the calls a GA program builds CSR offsets with, compresses a vector by a mask and expands it
+   again.  Collective, GA_Sync on entry and exit; the arrays are 1-D; lo and hi are C subscripts,
+   inclusive.  All six value types and all six mask types, in any combination.  A mask element is
+   set when it is non-zero (complex: either part; -0.0 is not set, a NaN is).  Set mask elements
+   outside [lo, hi] are ignored, and elements of g_dst outside [lo, hi] are never written.  Each rank
+   runs the kernels of ga_amd.h (gaamd_enum, gaamd_scan_tail + gaamd_scan, gaamd_mask_count +
+   gaamd_mask_pack / gaamd_mask_unpack) on its own part of the range; a rank that owns nothing of it
+   launches nothing and takes part in the exchange and the syncs.
+     GA_Patch_enum(g_a, lo, hi, start, inc)   a[i] = *start + (T)(i - lo) * *inc, lo <= i <= hi
+   (complex part by part; integers wrap).
+     GA_Scan_copy(g_src, g_dst, g_msk, lo, hi)        dst[i] = src at the last set element in [lo, i];
+                                                      zero before the first set one
+     GA_Scan_add(g_src, g_dst, g_msk, lo, hi, excl)   dst[i] = src[s] + ... + src[i], s the last set
+                                                      element in [lo, i]; excl != 0: ... + src[i-1], zero
+                                                      at s; elements before the first set one are NOT
+                                                      written (scan_addc.c:116-134 is the meaning)
+   Across ranks: each rank reduces its part (has a set element, open value at its end), the ranks
+   exchange these pairs bit for bit (one slot per rank of a zeroed array, armci_msg_lgop "+"), and
+   each rank forms its carry on the host: the tail of the nearest rank before it, in block order,
+   that holds a set element, plus -- for the adds -- the tails of the ranks between in ascending
+   order; then it scans its part with that carry.  For the integer types and for exactly summable
+   data the results are the same bits on any number of ranks and any block map; for inexact
+   floating-point data they are the same bits on every call for a given rank count and map, and
+   depend on how the array is cut, as GA_Norm1's and the dot products' do (summation order: ga_amd.h).
+   DEPARTURES from sparse.c: its second phase -- a pnga_gather of partial results from the ranks
+   between and a local fix-up loop (409-434) -- and its remote pnga_get of one element of g_src in
+   the exclusive case (378-382) are both replaced by the carry above; nothing is fetched from
+   another rank's block.
+     GA_Pack(g_src, g_dst, g_msk, lo, hi, icount)     dst[k] = src[f_k], f_k the k-th set element of
+                                                      [lo, hi], k from 0; *icount = their number
+     GA_Unpack(g_src, g_dst, g_msk, lo, hi, icount)   dst[f_k] = src[k]; the other elements stay
+   Bit copies.  Each rank counts its set elements, the ranks exchange the counts, a rank's place is
+   the sum of the counts before it in block order.  The packed side (g_dst of pack, g_src of
+   unpack) may have any block map: where the rank's range of it lies in its own block the kernel
+   works there in place, otherwise through HBM scratch and NGA_Put's / NGA_Get's path (a put is
+   complete at its owner before the closing sync); the scratch is freed before return.  The packed
+   side must hold *icount elements: otherwise every rank ends through GA_Error with a message that
+   names both numbers, and nothing was moved (the reference does not check this).
+   Aborts through GA_Error on every rank, before the first sync or launch: an array of rank other
+   than 1; lo > hi or a range outside the array; value types that differ; g_src == g_dst; block maps
+   of g_src and g_msk that differ (scans, pack) or of g_dst and g_msk (scans, unpack); an array in
+   a host segment; a missing icount, start or inc.  The *64 forms are not provided. */
+void GA_Patch_enum(int g_a, int lo, int hi, void *start, void *inc);
+void GA_Scan_copy(int g_src, int g_dst, int g_msk, int lo, int hi);
+void GA_Scan_add(int g_src, int g_dst, int g_msk, int lo, int hi, int excl);
+void GA_Pack(int g_src, int g_dst, int g_msk, int lo, int hi, int *icount);
+void GA_Unpack(int g_src, int g_dst, int g_msk, int lo, int hi, int *icount);
 /* global arrays alive on this rank (temporaries of the general path are destroyed
    before their call returns) */
 int gaamd_ga_live_arrays(void);

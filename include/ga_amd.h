@@ -211,6 +211,89 @@ int gaamd_diagonal(int op, int fn, long long n, void *a, long long a_step, void 
                    const void *scalar /* SHIFT only */, void *stream);
 int gaamd_scale_rows(int op, long long rows, long long cols, void *a, long long lda, const void *v, void *stream);
 int gaamd_scale_cols(int op, long long rows, long long cols, void *a, long long lda, const void *v, void *stream);
+/* The kernels under GA's sparse.c calls (ga.h: GA_Patch_enum, GA_Scan_copy, GA_Scan_add, GA_Pack,
+ * GA_Unpack), global/src/sparse.c expression for expression, no FMA: enumerate, the segmented
+ * scans, and stream compaction by a mask.  Arrays are contiguous and 1-D, n is in elements, every
+ * index and byte offset is 64-bit.  op is the value type and mop the mask type, both COMEX_ACC_*
+ * codes; all six types on both sides, in any combination.  Integers in unsigned (wraparound)
+ * arithmetic; complex part by part.
+ * A mask element is SET when it is non-zero (neq_zero_reg / neq_zero_cpl of abstract_ops.h): for
+ * complex when either part is; -0.0 is not set, a NaN is, a denormal is.
+ * (The names gaamd_pack / gaamd_unpack are the strided pack and unpack of section 2; the
+ * compaction is gaamd_mask_pack / gaamd_mask_unpack.)
+ *
+ * gaamd_enum: dst[i] = start + (T)(first + i) * stride, i < n (sparse.c:59-76): first + i is a
+ * 64-bit integer converted to the element type (integers: truncated), one product, one sum;
+ * complex re = start.re + (R)(first + i) * stride.re and im likewise.  start and stride are one
+ * host element each.  Returns with the kernel in flight.
+ *
+ * The segmented scans.  A segment starts at every set element.  fn:
+ *   GAAMD_SCAN_COPY      dst[i] = src[s], s the last set index at or before i: a bit copy (NaN
+ *                        payloads and -0.0 survive).  Elements before the first set one are
+ *                        written ZERO (sparse.c:196-206).
+ *   GAAMD_SCAN_ADD       dst[i] = src[s] + ... + src[i] (inclusive).  Elements before the first set
+ *                        one are NOT WRITTEN (sparse.c:361-365, scan_addc.c:116-134).
+ *   GAAMD_SCAN_ADD_EXCL  dst[i] = src[s] + ... + src[i-1]; +0 at i == s.  (The reference's loop
+ *                        starts the sum from that zero: the two differ only where every term is
+ *                        -0.0, which comes out as -0.0 here.)
+ * open != 0: a segment is open on entry and *carry (host, one element) is its value so far --
+ * the leftmost term of every sum up to the first set element, for COPY the value copied there.
+ * gaamd_scan returns with its kernels in flight.  dst must not overlap src or msk.
+ * gaamd_scan_tail is the reduction half, for the ranks of a distributed scan: *has_flag = 1 when
+ * any element is set; *tail = the open value at the end of the range -- ADD (either): the sum
+ * of src from the last set element to n - 1, of the whole range when none is set; COPY: the bits
+ * of src at the last set element, zero when none is set.  One pass over src and msk.  It
+ * synchronises its stream and writes both host outputs.  The next range's gaamd_scan takes
+ * (open = has_flag or an earlier range's, carry = tail combined on the host).
+ *
+ * The compaction.  With f_k the k-th set element: gaamd_mask_count writes their number to *count
+ * (host) after synchronising; gaamd_mask_pack packed[k] = src[f_k]; gaamd_mask_unpack
+ * dst[f_k] = packed[k], the unset elements of dst are not written, nor is packed past the count.
+ * Bit copies of 4-, 8- or 16-byte elements.  Both return with their kernels in flight.  The written
+ * side must not overlap the other two (packed judged at n elements).
+ *
+ * Shape: reduce, then scan -- three launches, and no workgroup ever waits for another (no
+ * look-back, no grid barrier), no atomics.  (1) one workgroup per tile of gaamd_scan_tile()
+ * elements computes the tile's aggregate: (a set element present, the open value at the tile's
+ * end), or the tile's set count; (2) ONE workgroup scans the aggregates in tile order,
+ * gaamd_scan_agg_span() of them per pass of its loop; (3) one workgroup per tile redoes its tile
+ * from its prefix and writes.  The aggregates live in the calling thread's device scratch
+ * (gaamd_patch_dot's, recycled call to call, freed at comex_finalize): calls of one thread that
+ * are in flight together must be on one stream.
+ *
+ * SUMMATION ORDER, a contract.  The combine (f1, v1) (+) (f2, v2) = (f1 | f2, f2 ? v2 : v1 + v2)
+ * is associative, so integer results are exact in any tree.  For float, double and the complex
+ * types the tree is fixed: a lane folds its 8 consecutive elements left to right; the 64 lanes of
+ * a wave are combined by the scan steps 1, 2, 4, 8, 16, 32 (at each step lane l takes the value
+ * of lane l - step on its left); the 4 waves of a workgroup in order; the tiles by the same
+ * procedure with 4 aggregates per lane, the passes in order; an element's result is
+ *   ((((carry (+) tiles before) (+) waves before) (+) lanes before) (+) elements before) (+) x.
+ * The same input therefore gives the same bits on every run.  Exactly summable data (every
+ * partial sum representable) give the sequential loop's bits; inexact data need not, and stay
+ * within the error bound of any summation order.  The identity is -0.0 (-0.0 + x has the bits of
+ * x), so empty prefixes and positions past n change no bit.
+ *
+ * Access: a lane's 8 consecutive elements move as 16-byte vectors where the base is 16-byte
+ * aligned, as 8- or 4-byte ones otherwise; bases need 4-byte alignment only.
+ * Negative codes, all before any launch or allocation, in this order: -3 a negative n; -4 an
+ * unknown op, mop or fn; -5 a missing pointer or host output (carry with open != 0); -7 n above
+ * GAAMD_SCAN_MAX_N; -8 a base below 4-byte alignment; -11 a forbidden overlap.  n == 0: 0 and no
+ * launch, the host outputs written (count 0, has_flag 0, tail zero).  gaamd_scan_tile: -4 for an
+ * unknown type. */
+#define GAAMD_SCAN_COPY 1
+#define GAAMD_SCAN_ADD 2
+#define GAAMD_SCAN_ADD_EXCL 3
+#define GAAMD_SCAN_MAX_N (1ll << 34)
+int gaamd_scan_tile(int op, int mop);   /* elements per tile (workgroup) */
+int gaamd_scan_agg_span(void);          /* tile aggregates per pass of launch (2)'s loop */
+int gaamd_enum(int op, long long n, long long first, const void *start, const void *stride, void *dst, void *stream);
+int gaamd_scan_tail(int op, int fn, int mop, long long n, const void *src, const void *msk,
+                    int *has_flag /* host */, void *tail /* host, one element */, void *stream);
+int gaamd_scan(int op, int fn, int mop, long long n, const void *src, const void *msk, void *dst, int open,
+               const void *carry /* host, one element; open != 0 only */, void *stream);
+int gaamd_mask_count(int mop, long long n, const void *msk, long long *count /* host */, void *stream);
+int gaamd_mask_pack(int op, int mop, long long n, const void *src, const void *msk, void *packed, void *stream);
+int gaamd_mask_unpack(int op, int mop, long long n, const void *packed, const void *msk, void *dst, void *stream);
 /* Row-major GEMM on the gfx950 matrix cores, for op = COMEX_ACC_DBL (v_mfma_f64_16x16x4_f64)
  * and COMEX_ACC_FLT (v_mfma_f32_16x16x4_f32); the kernel under GA_Dgemm / GA_Sgemm (ga.h):
  *   C[i][j] = alpha * sum_k op(A)[i][k] * op(B)[k][j] + beta * C[i][j],  i < m, j < n, kk < k
