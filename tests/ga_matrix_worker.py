@@ -25,10 +25,10 @@ import numpy as np  # noqa: E402
 import ga_amd  # noqa: E402
 import test_gpu_ga_math as K  # noqa: E402
 import test_gpu_matrix as M  # noqa: E402
-from ga_math_worker import C_DBL, C_DCPL, C_FLOAT, C_INT, C_LONG, GA, blocks_of, vp  # noqa: E402
+from ga_math_worker import C_DBL, C_DCPL, C_FLOAT, C_INT, C_LONG, C_SCPL, GA, blocks_of, vp  # noqa: E402
 
 TYPES = (C_DBL, C_FLOAT, C_INT, C_LONG, C_DCPL)   # one complex type for the scale and diagonal calls
-NORM_TYPES = (C_DBL, C_FLOAT, C_INT, C_LONG)
+NORM_TYPES = (C_DBL, C_FLOAT, C_INT, C_LONG, C_DCPL, C_SCPL)   # C_SCPL: norm_call's armci_msg_fgop branch
 SHAPES = ([37, 53], [53, 37], [40, 40])
 
 
@@ -167,7 +167,7 @@ def norm_call(L, a, which):
 def norms(L, rank, size):
     live = L.gaamd_ga_live_arrays()
     for dims in SHAPES + ([300], [2]):
-        for t in NORM_TYPES + (C_DCPL,):
+        for t in NORM_TYPES:
             for irreg in (False, True):
                 if irreg and len(dims) == 1:
                     continue
