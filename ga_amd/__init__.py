@@ -343,6 +343,34 @@ def gemm_plan(op, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc):
     return rc, {"tm": out[0], "tn": out[1], "tk": out[2], "grid_m": out[3], "grid_n": out[4], "ksteps": out[5]}
 
 
+# row-major complex GEMM on the matrix cores (gaamd_gemm_cplx): op is COMEX_ACC_DCP or
+# COMEX_ACC_CPL, trans one of N T C, alpha and beta Python complex (None reaches the library
+# as NULL), ld in complex elements; the return code is handed back
+def _cplx_scalar(op, v):
+    """one complex element for the `void *` scalar: complex64 for COMEX_ACC_CPL, else complex128"""
+    if v is None:
+        return None, None
+    a = np.array([v], dtype=np.complex64 if op == COMEX_ACC_CPL else np.complex128)
+    return a, a.ctypes.data_as(ctypes.c_void_p)
+
+
+def gemm_cplx(op, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, stream=None):
+    al, ap = _cplx_scalar(op, alpha)
+    be, bp = _cplx_scalar(op, beta)
+    return lib().gaamd_gemm_cplx(op, _trans(transa), _trans(transb), m, n, k, ap, ctypes.c_void_p(a), lda,
+                                 ctypes.c_void_p(b), ldb, bp, ctypes.c_void_p(c), ldc, stream)
+
+
+def gemm_cplx_plan(op, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc):
+    """gaamd_gemm_cplx's checks without a launch (no GPU): (code, {tm, tn, tk, grid_m, grid_n, ksteps})"""
+    al, ap = _cplx_scalar(op, alpha)
+    be, bp = _cplx_scalar(op, beta)
+    out = (ctypes.c_longlong * 6)()
+    rc = lib().gaamd_gemm_cplx_plan(op, _trans(transa), _trans(transb), m, n, k, ap, ctypes.c_void_p(a), lda,
+                                    ctypes.c_void_p(b), ldb, bp, ctypes.c_void_p(c), ldc, out)
+    return rc, {"tm": out[0], "tn": out[1], "tk": out[2], "grid_m": out[3], "grid_n": out[4], "ksteps": out[5]}
+
+
 # row-major transpose through LDS tiles (gaamd_transpose): src, dst are device addresses,
 # ld in elements; the return code is handed back
 def transpose(op, rows, cols, src, lds, dst, ldd, stream=None):

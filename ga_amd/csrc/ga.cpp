@@ -1490,7 +1490,7 @@ void NGA_Select_elem(int g_a, char *op, void *val, int *index) {
     }
 }
 
-// ---- GA_Dgemm / GA_Sgemm / NGA_Matmul_patch ----------------------------------------
+// ---- GA_Dgemm / GA_Sgemm / GA_Zgemm / GA_Cgemm / NGA_Matmul_patch -------------------
 // pnga_matmul (global/src/matmul.c) gets chunks of A and B to host buffers, multiplies
 // them with a host BLAS and accumulates the products into C.  Here every block is in HBM
 // and the owner computes: a rank cuts the C patch by its own block and, for every panel of
@@ -1500,11 +1500,16 @@ void NGA_Select_elem(int g_a, char *op, void *val, int *index) {
 // through their mappings) and runs gaamd_gemm into its block in place: the caller's beta
 // on the first panel, beta = 1 on the later ones.  The panels and the kernel's summation
 // order depend on neither the block maps nor the rank count, so neither do the bits of C.
+// C_DCPL and C_SCPL arrays (which the reference hands to a host zgemm / cgemm) go the same
+// way through gaamd_gemm_cplx, whose beta == (1,0) adds C exactly; for them alone trans may
+// be 'C' 'c', the conjugate transpose, its patch stored as for 'T'.
 constexpr long kGemmPanel = 1024;
 
-static bool is_trans(char t, const char *what) {
+static bool is_trans(char t, const char *what, bool cplx) {
     if (t == 'n' || t == 'N') return false;
     if (t == 't' || t == 'T') return true;
+    if (cplx && (t == 'c' || t == 'C')) return true;
+    if (cplx) fatal("%s: trans '%c' is not one of N n T t C c", what, t);
     fatal("%s: trans '%c' is not one of N n T t", what, t);
 }
 
@@ -1518,8 +1523,10 @@ static void matmul_patch(int type, char transa, char transb, const void *alpha, 
                          const long *alo, const long *ahi, int g_b, const long *blo, const long *bhi, int g_c,
                          const long *clo, const long *chi, const char *what) {
     GArray &a = arr(g_a), &b = arr(g_b), &c = arr(g_c);
-    const bool ta = is_trans(transa, what), tb = is_trans(transb, what);
-    if (c.type != C_DBL && c.type != C_FLOAT) fatal("%s: type %d is neither C_DBL nor C_FLOAT", what, c.type);
+    const bool cplx = c.type == C_DCPL || c.type == C_SCPL;
+    const bool ta = is_trans(transa, what, cplx), tb = is_trans(transb, what, cplx);
+    if (c.type != C_DBL && c.type != C_FLOAT && !cplx)
+        fatal("%s: type %d is none of C_DBL, C_FLOAT, C_DCPL, C_SCPL", what, c.type);
     if (a.type != c.type || b.type != c.type) fatal("%s: types of the arrays differ", what);
     if (type && c.type != type)
         fatal("%s: type mismatch: arrays of type %d in a call for type %d", what, c.type, type);
@@ -1550,9 +1557,9 @@ static void matmul_patch(int type, char transa, char transb, const void *alpha, 
         const long kmax = std::min(k, kGemmPanel);
         void *pa = gaamd_dev_malloc((size_t)mi * kmax * c.elemsize), *pb = gaamd_dev_malloc((size_t)kmax * nj * c.elemsize);
         if (!pa || !pb) fatal("%s: no device memory for the panel buffers", what);
-        const double one_d = 1.0;
-        const float one_f = 1.0f;
-        const void *one = c.type == C_DBL ? (const void *)&one_d : (const void *)&one_f;
+        const double one_d[2] = {1.0, 0.0};   // 1, or (1,0) for the complex types
+        const float one_f[2] = {1.0f, 0.0f};
+        const void *one = c.type == C_DBL || c.type == C_DCPL ? (const void *)one_d : (const void *)one_f;
         for (long kp = 0; kp < k; kp += kGemmPanel) {
             const long kl = std::min(kGemmPanel, k - kp);
             long lo[2], hi[2], ld[1];
@@ -1570,8 +1577,8 @@ static void matmul_patch(int type, char transa, char transb, const void *alpha, 
             hi[1] = lo[1] + (tb ? nj : kl) - 1;
             const long ldb = ld[0] = hi[0] - lo[0] + 1;
             patch_op(GA_GET, g_b, lo, hi, pb, ld, nullptr);
-            const int rc = gaamd_gemm(c.optype, transa, transb, mi, nj, kl, alpha, pa, lda, pb, ldb, kp ? one : beta,
-                                      sc.p, sc.ext[0], gaamd_stream());
+            const int rc = (cplx ? gaamd_gemm_cplx : gaamd_gemm)(c.optype, transa, transb, mi, nj, kl, alpha, pa, lda, pb,
+                                                                 ldb, kp ? one : beta, sc.p, sc.ext[0], gaamd_stream());
             if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
             // the next panel's gets overwrite the buffers
             if (gaamd_sync(gaamd_stream()) != 0) fatal("%s: the stream failed", what);
@@ -1586,7 +1593,8 @@ static void matmul_patch(int type, char transa, char transb, const void *alpha, 
 static void c_gemm(int type, char ta, char tb, int m, int n, int k, const void *alpha, int g_a, int g_b,
                    const void *beta, int g_c, const char *what) {
     // the leading corners, as stored: A m x k (k x m for 'T'), B k x n (n x k), C m x n
-    const bool tra = is_trans(ta, what), trb = is_trans(tb, what);
+    const bool cplx = type == C_DCPL || type == C_SCPL;
+    const bool tra = is_trans(ta, what, cplx), trb = is_trans(tb, what, cplx);
     const long one[2] = {1, 1};
     const long ah[2] = {tra ? m : k, tra ? k : m}, bh[2] = {trb ? k : n, trb ? n : k}, ch[2] = {n, m};
     matmul_patch(type, ta, tb, alpha, beta, g_a, one, ah, g_b, one, bh, g_c, one, ch, what);
@@ -1597,6 +1605,14 @@ void GA_Dgemm(char ta, char tb, int m, int n, int k, double alpha, int g_a, int 
 }
 void GA_Sgemm(char ta, char tb, int m, int n, int k, float alpha, int g_a, int g_b, float beta, int g_c) {
     c_gemm(C_FLOAT, ta, tb, m, n, k, &alpha, g_a, g_b, &beta, g_c, "GA_Sgemm");
+}
+void GA_Zgemm(char ta, char tb, int m, int n, int k, DoubleComplex alpha, int g_a, int g_b, DoubleComplex beta,
+              int g_c) {
+    c_gemm(C_DCPL, ta, tb, m, n, k, &alpha, g_a, g_b, &beta, g_c, "GA_Zgemm");
+}
+void GA_Cgemm(char ta, char tb, int m, int n, int k, SingleComplex alpha, int g_a, int g_b, SingleComplex beta,
+              int g_c) {
+    c_gemm(C_SCPL, ta, tb, m, n, k, &alpha, g_a, g_b, &beta, g_c, "GA_Cgemm");
 }
 void NGA_Matmul_patch(char transa, char transb, void *alpha, void *beta, int g_a, int alo[], int ahi[], int g_b,
                       int blo[], int bhi[], int g_c, int clo[], int chi[]) {

@@ -12,4 +12,5 @@
 #include "gaamd_matrix.hip"
 #include "gaamd_scan.hip"
 #include "gaamd_gemm.hip"
+#include "gaamd_gemm_cplx.hip"
 #include "gaamd_transpose.hip"

@@ -201,6 +201,21 @@ int plan_gemm(int op, int transa, int transb, long long m, long long n, long lon
               const void *a, long long lda, const void *b, long long ldb, const void *beta, const void *c,
               long long ldc, long long plan[6]);
 
+// ---- row-major complex GEMM on the matrix cores (gaamd_gemm_cplx.hip; ga_amd.h gaamd_gemm_cplx) ----
+// op = COMEX_ACC_DCP or COMEX_ACC_CPL; trans N T C in either case; ld in complex elements;
+// launch_gemm's codes, kPatchErrAlign below the alignment of the element's real part.
+// The workgroup's tile of C and its k step, per op (the wave tile is 64 x TN / 2):
+constexpr int kCGemmTM = 128;
+constexpr int kCGemmTN_DCP = 64, kCGemmTK_DCP = 16;
+constexpr int kCGemmTN_CPL = 128, kCGemmTK_CPL = 16;
+int launch_gemm_cplx(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
+                     const void *a, long long lda, const void *b, long long ldb, const void *beta, void *c,
+                     long long ldc, hipStream_t stream);
+// plan[0..5] as plan_gemm's, with the op's own tile constants
+int plan_gemm_cplx(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
+                   const void *a, long long lda, const void *b, long long ldb, const void *beta, const void *c,
+                   long long ldc, long long plan[6]);
+
 // ---- row-major transpose through LDS (gaamd_transpose.hip; ga_amd.h gaamd_transpose) ----
 // op: any COMEX_ACC_* type (transpose, for the element size) or DBL / FLT (transpose_acc);
 // ld in elements; the codes are the patch codes above, with gaamd_gemm's meanings.

@@ -177,6 +177,18 @@ int gaamd_gemm_plan(int op, int transa, int transb, long long m, long long n, lo
     return plan_gemm(op, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, plan);
 }
 
+int gaamd_gemm_cplx(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
+                    const void *a, long long lda, const void *b, long long ldb, const void *beta, void *c, long long ldc,
+                    void *stream) {
+    return launch_gemm_cplx(op, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, stream_of(stream));
+}
+
+int gaamd_gemm_cplx_plan(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
+                         const void *a, long long lda, const void *b, long long ldb, const void *beta, const void *c,
+                         long long ldc, long long plan[6]) {
+    return plan_gemm_cplx(op, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, plan);
+}
+
 int gaamd_transpose(int op, long long rows, long long cols, const void *src, long long lds, void *dst, long long ldd,
                     void *stream) {
     return launch_transpose(op, rows, cols, src, lds, dst, ldd, stream_of(stream));

@@ -144,9 +144,24 @@ DoubleComplex NGA_Zdot_patch(int g_a, char t_a, int alo[], int ahi[], int g_b, c
    C_FLOAT, differs between the arrays or does not match the call; a rank other than 2;
    a trans other than N n T t; a patch out of range; patch extents that do not agree; an
    array in a host segment; g_c equal to g_a or g_b with patches that overlap (an owner
-   would read what another rank is writing). */
+   would read what another rank is writing).
+   Complex arrays (capi.c GA_Zgemm, GA_Cgemm, which the reference hands to a host zgemm /
+   cgemm): GA_Zgemm on C_DCPL, GA_Cgemm on C_SCPL and NGA_Matmul_patch on either run the
+   same loop over gaamd_gemm_cplx (ga_amd.h), with beta = (1,0) on the later panels, which
+   that kernel adds exactly.  For complex arrays, and only for them, trans may also be
+   'C' 'c': op(X) is the conjugate transpose, the stored patch shaped as for 'T'.  Rank
+   independence holds as above with gaamd_gemm_cplx's order contract: two accumulators per
+   element from +0, four real products per complex product in a fixed sequence, increasing
+   k within a panel, then alpha * acc + beta * C part by part without FMA.  Aborts: as
+   above with C_DCPL / C_SCPL among the types; 'C' 'c' on real arrays (GA_Dgemm, GA_Sgemm
+   and NGA_Matmul_patch on them answer as before); GA_Zgemm / GA_Cgemm on arrays of
+   another type. */
 void GA_Dgemm(char ta, char tb, int m, int n, int k, double alpha, int g_a, int g_b, double beta, int g_c);
 void GA_Sgemm(char ta, char tb, int m, int n, int k, float alpha, int g_a, int g_b, float beta, int g_c);
+void GA_Zgemm(char ta, char tb, int m, int n, int k, DoubleComplex alpha, int g_a, int g_b, DoubleComplex beta,
+              int g_c);
+void GA_Cgemm(char ta, char tb, int m, int n, int k, SingleComplex alpha, int g_a, int g_b, SingleComplex beta,
+              int g_c);
 void NGA_Matmul_patch(char transa, char transb, void *alpha, void *beta, int g_a, int alo[], int ahi[],
                       int g_b, int blo[], int bhi[], int g_c, int clo[], int chi[]);
 /* values of k per panel of the owner-computes loop (a fixed constant, 1024) */

@@ -328,6 +328,37 @@ int gaamd_gemm(int op, int transa, int transb, long long m, long long n, long lo
 int gaamd_gemm_plan(int op, int transa, int transb, long long m, long long n, long long k,
                     const void *alpha, const void *a, long long lda, const void *b, long long ldb,
                     const void *beta, const void *c, long long ldc, long long plan[6]);
+/* Row-major complex GEMM on the gfx950 matrix cores, for op = COMEX_ACC_DCP
+ * (v_mfma_f64_16x16x4_f64 on the parts) and COMEX_ACC_CPL (v_mfma_f32_16x16x4_f32); the kernel
+ * under GA_Zgemm / GA_Cgemm (ga.h).  gaamd_gemm's argument list, expression and storage rules,
+ * with elements interleaved (re, im), alpha and beta pointing at one complex element and ld in
+ * COMPLEX ELEMENTS.  op(X) = X for trans 'N'/'n', its transpose for 'T'/'t', its conjugate
+ * transpose for 'C'/'c' (stored as for 'T').  Bases aligned to the element's real part (8 / 4
+ * bytes) are enough; all offsets are 64-bit.
+ * Summation order (a contract): trans 'C' negates the imaginary part first, exactly.  Every
+ * element of C has two accumulators, re and im, both starting at +0.  For each group of four
+ * consecutive k, counted from 0 in increasing order, re takes the matrix-core instruction over
+ * a.re * b.re, then the one over -a.im * b.im; im takes the one over a.re * b.im, then the one
+ * over a.im * b.re -- four real products per complex product, never three.  Nothing depends
+ * on where the element lies in C or in the launch grid, nor on m and n: a sub-rectangle of C
+ * computed alone has the bits it has in the whole product, and so has every repeat of a call.
+ * Then, with s the accumulators and no FMA: t.re = al.re * s.re - al.im * s.im,
+ * t.im = al.re * s.im + al.im * s.re; u = beta * c formed the same way; c = t + u part by
+ * part.  beta == (0,0): C is not read and c = t.  beta exactly (1,0): c = t + c with no
+ * products on C -- exact, so a -0 or an infinity there is not turned into something else by a
+ * multiplication.  alpha == (0,0) or k == 0: A and B are not read and C = beta * C
+ * (gaamd_patch_scale for that op; all zeros when beta == (0,0) too).  m == 0 or n == 0: 0, no
+ * launch.
+ * Negative codes and the overlap rule are gaamd_gemm's: -4 is an op other than DCP / CPL or a
+ * trans other than N n T t C c, -8 a base below the alignment of the real part.
+ * gaamd_gemm_cplx_plan: gaamd_gemm_plan's answers; the tile constants differ between the two
+ * ops and from gaamd_gemm's. */
+int gaamd_gemm_cplx(int op, int transa, int transb, long long m, long long n, long long k,
+                    const void *alpha, const void *a, long long lda, const void *b, long long ldb,
+                    const void *beta, void *c, long long ldc, void *stream);
+int gaamd_gemm_cplx_plan(int op, int transa, int transb, long long m, long long n, long long k,
+                         const void *alpha, const void *a, long long lda, const void *b, long long ldb,
+                         const void *beta, const void *c, long long ldc, long long plan[6]);
 /* Row-major transpose through LDS tiles; the kernels under GA_Transpose / GA_Symmetrize (ga.h).
  *   gaamd_transpose:      dst[j][i] = src[i][j],  i < rows, j < cols
  *     src is rows x cols, dst is cols x rows.  A pure bit copy: op is any COMEX_ACC_* code and
