@@ -38,6 +38,7 @@
 #include <string.h>
 #include <algorithm>
 #include <functional>
+#include <limits>
 #include <thread>
 #include <string>
 #include <vector>
@@ -617,6 +618,56 @@ static void gatscat(GatScat op, int g_a, void *v, int *const *csubs, const int *
 static void c2f_index(int nd, const int *c, long *f) { for (int i = 0; i < nd; i++) f[nd - i - 1] = (long)c[i] + 1; }
 static void c2f(int nd, const int *c, long *f) { for (int i = 0; i < nd; i++) f[nd - i - 1] = c[i]; }
 
+// a patch in internal order (Fortran order, 1-based, inclusive), from the C subscripts of
+// a call; without subscripts (clo == nullptr) the whole array
+struct Patch {
+    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
+    Patch() {}
+    Patch(const GArray &a, const int *clo, const int *chi) {
+        if (clo) {
+            c2f_index(a.ndim, clo, lo);
+            c2f_index(a.ndim, chi, hi);
+        } else {
+            for (int d = 0; d < a.ndim; d++) { lo[d] = 1; hi[d] = a.dims[d]; }
+        }
+    }
+    Patch(long lo0, long hi0) { lo[0] = lo0; hi[0] = hi0; }   // elements [lo0, hi0] of a 1-D array
+};
+
+// NGA_Put's (lo, hi, ld) in internal order
+struct PatchLd {
+    Patch p;
+    long ld[GA_MAX_DIM] = {0};
+    PatchLd(const GArray &a, const int *clo, const int *chi, const int *cld) : p(a, clo, chi) {
+        if (a.ndim > 1) c2f(a.ndim - 1, cld, ld);
+    }
+};
+
+// pnga_allocate (base.c:2550-2630): the block sizes and the process grid ddb picks for
+// `npes` processes from dims and chunk (Fortran order; chunk[0] == 0: no chunk given)
+static void proc_grid(int ndim, const long *fdims, const long *fchunk, long npes, long *blk, long *pe) {
+    if (fchunk[0] != 0)
+        for (int d = 0; d < ndim; d++) blk[d] = std::min(fchunk[d], fdims[d]);
+    else
+        for (int d = 0; d < ndim; d++) blk[d] = -1;
+    for (int d = 0; d < ndim; d++) if (fdims[d] == 1) blk[d] = 1;
+    ddb(ndim, fdims, npes, blk, pe);
+}
+
+// Which armci_msg_?gop carries which GA type: the one on the type's real component type.
+// f(buf as a pointer to that type, the gop) -- the caller passes its count (2 for the parts
+// of a complex value) and operator, and reads the typed result.
+template <class F>
+static void gop_by_type(int type, void *buf, F &&f) {
+    switch (type) {
+    case C_INT: f((int *)buf, armci_msg_igop); break;
+    case C_LONG: f((long *)buf, armci_msg_lgop); break;
+    case C_FLOAT:
+    case C_SCPL: f((float *)buf, armci_msg_fgop); break;
+    default: f((double *)buf, armci_msg_dgop); break;
+    }
+}
+
 }  // namespace gaamd_ga
 
 using namespace gaamd_ga;
@@ -657,12 +708,7 @@ int NGA_Create(int type, int ndim, int dims[], char *name, int chunk[]) {
     }
     // pnga_allocate (base.c:2550-2630)
     long blk[GA_MAX_DIM], pe[GA_MAX_DIM];
-    if (fchunk[0] != 0)
-        for (int d = 0; d < ndim; d++) blk[d] = std::min(fchunk[d], fdims[d]);
-    else
-        for (int d = 0; d < ndim; d++) blk[d] = -1;
-    for (int d = 0; d < ndim; d++) if (fdims[d] == 1) blk[d] = 1;
-    ddb(ndim, fdims, world_size(), blk, pe);
+    proc_grid(ndim, fdims, fchunk, world_size(), blk, pe);
     for (int d = 0; d < ndim; d++) {
         long pcut;
         if (fchunk[d] > 1) {
@@ -736,34 +782,26 @@ void NGA_Distribution(int g_a, int iproc, int lo[], int hi[]) {
 // the reference returns -1 -- so does this.
 int NGA_Locate_num_blocks(int g_a, int lo[], int hi[]) {
     GArray &a = arr(g_a);
-    long flo[GA_MAX_DIM], fhi[GA_MAX_DIM];
-    c2f_index(a.ndim, lo, flo);
-    c2f_index(a.ndim, hi, fhi);
+    const Patch p(a, lo, hi);
     for (int d = 0; d < a.ndim; d++)
-        if (flo[d] < 1 || fhi[d] > a.dims[d] || flo[d] > fhi[d]) fatal("Requested region out of bounds");
+        if (p.lo[d] < 1 || p.hi[d] > a.dims[d] || p.lo[d] > p.hi[d]) fatal("Requested region out of bounds");
     return -1;
 }
 
 static void c_patch(GaOp kind, int g_a, int lo[], int hi[], void *buf, int ld[], void *alpha) {
-    GArray &a = arr(g_a);
-    long flo[GA_MAX_DIM], fhi[GA_MAX_DIM], fld[GA_MAX_DIM] = {0};
-    c2f_index(a.ndim, lo, flo);
-    c2f_index(a.ndim, hi, fhi);
-    if (a.ndim > 1) c2f(a.ndim - 1, ld, fld);
-    patch_op(kind, g_a, flo, fhi, buf, fld, alpha);
+    const PatchLd f(arr(g_a), lo, hi, ld);
+    patch_op(kind, g_a, f.p.lo, f.p.hi, buf, f.ld, alpha);
 }
 
 // ---- strided (skip) and non-blocking variants: capi.c:1990-2060, 2103-2190 ----
 static void c_strided(GaOp kind, int g_a, int lo[], int hi[], int skip[], void *buf, int ld[], void *alpha) {
     GArray &a = arr(g_a);
-    long flo[GA_MAX_DIM], fhi[GA_MAX_DIM], fld[GA_MAX_DIM] = {0}, fskip[GA_MAX_DIM];
-    c2f_index(a.ndim, lo, flo);
-    c2f_index(a.ndim, hi, fhi);
-    if (a.ndim > 1) c2f(a.ndim - 1, ld, fld);
+    const PatchLd f(a, lo, hi, ld);
+    long fskip[GA_MAX_DIM];
     c2f(a.ndim, skip, fskip);   // COPYC2F: reversed, no +1
     for (int d = 0; d < a.ndim; d++)
         if (fskip[d] < 1) fatal("nga_strided: invalid skip %ld along coordinate %d", fskip[d], d);
-    patch_op(kind, g_a, flo, fhi, buf, fld, alpha, fskip);
+    patch_op(kind, g_a, f.p.lo, f.p.hi, buf, f.ld, alpha, fskip);
 }
 
 void NGA_Strided_acc(int g_a, int lo[], int hi[], int skip[], void *buf, int ld[], void *alpha) {
@@ -783,11 +821,7 @@ struct GaNb { bool used = false; bool get = false; std::vector<armci_hdl_t> h; }
 static std::vector<GaNb> g_ga_nb;
 
 static void c_nb(GaOp kind, int g_a, int lo[], int hi[], void *buf, int ld[], void *alpha, ga_nbhdl_t *nbhandle) {
-    GArray &a = arr(g_a);
-    long flo[GA_MAX_DIM], fhi[GA_MAX_DIM], fld[GA_MAX_DIM] = {0};
-    c2f_index(a.ndim, lo, flo);
-    c2f_index(a.ndim, hi, fhi);
-    if (a.ndim > 1) c2f(a.ndim - 1, ld, fld);
+    const PatchLd f(arr(g_a), lo, hi, ld);
     size_t slot = 0;
     while (slot < g_ga_nb.size() && g_ga_nb[slot].used) ++slot;
     if (slot == g_ga_nb.size()) g_ga_nb.emplace_back();
@@ -795,7 +829,7 @@ static void c_nb(GaOp kind, int g_a, int lo[], int hi[], void *buf, int ld[], vo
     n.used = true;
     n.get = kind == GA_GET;
     n.h.clear();
-    patch_op(kind, g_a, flo, fhi, buf, fld, alpha, nullptr, &n.h);
+    patch_op(kind, g_a, f.p.lo, f.p.hi, buf, f.ld, alpha, nullptr, &n.h);
     *nbhandle = (ga_nbhdl_t)(slot + 1);
 }
 
@@ -826,14 +860,13 @@ void NGA_Get(int g_a, int lo[], int hi[], void *buf, int ld[]) { c_patch(GA_GET,
 void NGA_Access(int g_a, int lo[], int hi[], void *ptr, int ld[]) {
     GArray &a = arr(g_a);
     const int me = my_rank();
-    long blo[GA_MAX_DIM], bhi[GA_MAX_DIM], flo[GA_MAX_DIM], fhi[GA_MAX_DIM];
+    long blo[GA_MAX_DIM], bhi[GA_MAX_DIM];
     block_elems(a, me, blo, bhi);
-    c2f_index(a.ndim, lo, flo);
-    c2f_index(a.ndim, hi, fhi);
+    const Patch p(a, lo, hi);
     long off = 0, f = 1;
     for (int d = 0; d < a.ndim; d++) {
-        if (flo[d] < blo[d] || fhi[d] > bhi[d]) fatal("NGA_Access: patch not local");
-        off += (flo[d] - blo[d]) * f;
+        if (p.lo[d] < blo[d] || p.hi[d] > bhi[d]) fatal("NGA_Access: patch not local");
+        off += (p.lo[d] - blo[d]) * f;
         f *= bhi[d] - blo[d] + 1;
     }
     comex_fence_all(COMEX_GROUP_WORLD);   // pending writes land before the caller reads
@@ -876,12 +909,7 @@ int gaamd_ga_proc_grid(int ndim, const int *dims, const int *chunk, int npes, in
     long fdims[GA_MAX_DIM], fchunk[GA_MAX_DIM] = {0}, blk[GA_MAX_DIM], pe[GA_MAX_DIM];
     c2f(ndim, dims, fdims);
     if (chunk) c2f(ndim, chunk, fchunk);
-    if (fchunk[0] != 0)
-        for (int d = 0; d < ndim; d++) blk[d] = std::min(fchunk[d], fdims[d]);
-    else
-        for (int d = 0; d < ndim; d++) blk[d] = -1;
-    for (int d = 0; d < ndim; d++) if (fdims[d] == 1) blk[d] = 1;
-    ddb(ndim, fdims, npes, blk, pe);
+    proc_grid(ndim, fdims, fchunk, npes, blk, pe);
     for (int i = 0; i < ndim; i++) grid[ndim - 1 - i] = (int)pe[i];
     return 0;
 }
@@ -901,8 +929,8 @@ int gaamd_ga_proc_grid(int ndim, const int *dims, const int *chunk, int npes, in
 // Transposes, reshapes and arrays in a host segment abort: nothing here computes on
 // the host.
 
-// this rank's part of the patch [lo, hi] (Fortran order, 1-based): its address in
-// the block, the counts and the byte strides the block's extents give
+// this rank's part of a patch: its address in the block, the counts and the byte
+// strides the block's extents give
 struct Sub {
     bool any = false;
     char *p = nullptr;
@@ -911,13 +939,13 @@ struct Sub {
     double bytes = 0;
 };
 
-static Sub own_sub(const GArray &a, const long *lo, const long *hi) {
+static Sub own_sub(const GArray &a, const Patch &p) {
     Sub s;
     long blo[GA_MAX_DIM], bhi[GA_MAX_DIM];
     if (block_elems(a, my_rank(), blo, bhi) == 0) return s;
     for (int d = 0; d < a.ndim; d++) {
-        s.plo[d] = std::max(lo[d], blo[d]);
-        s.phi[d] = std::min(hi[d], bhi[d]);
+        s.plo[d] = std::max(p.lo[d], blo[d]);
+        s.phi[d] = std::min(p.hi[d], bhi[d]);
         if (s.plo[d] > s.phi[d]) return s;
     }
     long long off = 0, f = 1;
@@ -942,9 +970,9 @@ static void need_hbm(const GArray &a, const char *what) {
               "computing on host-segment arrays is not supported", what, a.name.c_str());
 }
 
-static void check_patch(const GArray &a, const long *lo, const long *hi, const char *what) {
+static void check_patch(const GArray &a, const Patch &p, const char *what) {
     for (int d = 0; d < a.ndim; d++)
-        if (lo[d] < 1 || hi[d] > a.dims[d] || lo[d] > hi[d]) fatal("%s: patch out of range in dim %d", what, d);
+        if (p.lo[d] < 1 || p.hi[d] > a.dims[d] || p.lo[d] > p.hi[d]) fatal("%s: patch out of range in dim %d", what, d);
 }
 
 // pnga_compare_distr (base.c): equal shapes and equal block maps
@@ -955,17 +983,16 @@ static bool same_distr(const GArray &a, const GArray &b) {
     return true;
 }
 
-static bool same_patch(int nd, const long *alo, const long *ahi, const long *blo, const long *bhi) {
+static bool same_patch(int nd, const Patch &a, const Patch &b) {
     for (int d = 0; d < nd; d++)
-        if (alo[d] != blo[d] || ahi[d] != bhi[d]) return false;
+        if (a.lo[d] != b.lo[d] || a.hi[d] != b.hi[d]) return false;
     return true;
 }
 
 // patches of equal rank and extents (anything else is a reshape)
-static void need_same_shape(const GArray &a, const long *alo, const long *ahi, const GArray &b, const long *blo,
-                            const long *bhi, const char *what) {
+static void need_same_shape(const GArray &a, const Patch &pa, const GArray &b, const Patch &pb, const char *what) {
     bool same = a.ndim == b.ndim;
-    for (int d = 0; same && d < a.ndim; d++) same = ahi[d] - alo[d] == bhi[d] - blo[d];
+    for (int d = 0; same && d < a.ndim; d++) same = pa.hi[d] - pa.lo[d] == pb.hi[d] - pb.lo[d];
     if (!same)
         fatal("%s: patches of different rank or extents (a reshape) are not supported", what);
 }
@@ -974,14 +1001,39 @@ static void need_no_trans(char t, const char *what) {
     if (t != 'n' && t != 'N') fatal("%s: transposed patches (trans '%c') are not supported", what, t);
 }
 
-static void math_end(const char *what) {
+// how a launcher's return code ends a collective call.  zero_ok: GAAMD_ZERO_DIVISOR (the
+// element-wise calls) is not an error here -- returns 1 for the caller to combine over ranks
+static int launched(int rc, const char *what, bool zero_ok = false) {
+    if (zero_ok && rc == GAAMD_ZERO_DIVISOR) return 1;
+    if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+    return 0;
+}
+
+static void stream_wait(const char *what) {
     if (gaamd_sync(gaamd_stream()) != 0) fatal("%s: the stream failed", what);
+}
+
+static void math_end(const char *what) {
+    stream_wait(what);
     comex_barrier(COMEX_GROUP_WORLD);
 }
 
-static void whole(const GArray &a, long *lo, long *hi) {
-    for (int d = 0; d < a.ndim; d++) { lo[d] = 1; hi[d] = a.dims[d]; }
-}
+// HBM scratch of one call, freed when it goes out of scope (or by free(), earlier)
+struct Scratch {
+    void *p = nullptr;
+    Scratch() {}
+    Scratch(Scratch &&o) : p(o.p) { o.p = nullptr; }
+    Scratch &operator=(Scratch &&o) {
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~Scratch() { free(); }
+    void *alloc(size_t bytes) { return p = gaamd_dev_malloc(bytes); }   // null: the caller aborts with its message
+    void free() {
+        if (p) gaamd_dev_free(p);
+        p = nullptr;
+    }
+};
 
 int GA_Duplicate(int g_a, char *array_name) {
     GArray n = arr(g_a);   // type, shape and block map (pnga_duplicate, base.c)
@@ -1007,18 +1059,17 @@ int gaamd_ga_live_arrays(void) {
 }
 
 enum MapKind { M_FILL, M_SCALE };
-static void map_patch(MapKind kind, int g_a, const long *lo, const long *hi, const void *val, const char *what) {
+static void map_patch(MapKind kind, int g_a, const Patch &p, const void *val, const char *what) {
     GArray &a = arr(g_a);
     need_hbm(a, what);
-    check_patch(a, lo, hi, what);
+    check_patch(a, p, what);
     comex_barrier(COMEX_GROUP_WORLD);   // fences every pending one-sided operation, then syncs
-    const Sub s = own_sub(a, lo, hi);
+    const Sub s = own_sub(a, p);
     (kind == M_FILL ? g_stat.numfill : g_stat.numscale)++;
     if (s.any) {
-        const int rc = kind == M_FILL
-                           ? gaamd_patch_fill(a.optype, val, s.p, s.stride, s.count, a.ndim, gaamd_stream())
-                           : gaamd_patch_scale(a.optype, val, s.p, s.stride, s.count, a.ndim, gaamd_stream());
-        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        launched(kind == M_FILL ? gaamd_patch_fill(a.optype, val, s.p, s.stride, s.count, a.ndim, gaamd_stream())
+                                : gaamd_patch_scale(a.optype, val, s.p, s.stride, s.count, a.ndim, gaamd_stream()),
+                 what);
         g_stat.mathloc += s.bytes * (kind == M_FILL ? 1 : 2);
     }
     math_end(what);
@@ -1060,89 +1111,107 @@ static void local_copy(const Sub &s, const Sub &t, int nd, int esz, const char *
 // pnga_copy_patch (global.npatch.c:560-935), trans 'N', equal rank and extents: each
 // rank cuts the source patch by its own block and puts that part, from HBM, into g_b
 // at the shifted position; where both blocks coincide it is one local copy kernel
-static void copy_patch(int g_a, const long *alo, const long *ahi, int g_b, const long *blo, const long *bhi,
-                       const char *what) {
+static void copy_patch(int g_a, const Patch &pa, int g_b, const Patch &pb, const char *what) {
     GArray &a = arr(g_a), &b = arr(g_b);
     if (a.type != b.type) fatal("%s: types of '%s' and '%s' differ", what, a.name.c_str(), b.name.c_str());
     need_hbm(a, what);
     need_hbm(b, what);
     if (a.ndim != b.ndim) fatal("%s: arrays of different rank (a reshape) are not supported", what);
-    check_patch(a, alo, ahi, what);
-    check_patch(b, blo, bhi, what);
-    need_same_shape(a, alo, ahi, b, blo, bhi, what);
+    check_patch(a, pa, what);
+    check_patch(b, pb, what);
+    need_same_shape(a, pa, b, pb, what);
     const int nd = a.ndim;
-    if (g_a == g_b && !same_patch(nd, alo, ahi, blo, bhi)) {
+    if (g_a == g_b && !same_patch(nd, pa, pb)) {
         bool meet = true;
-        for (int d = 0; d < nd; d++) meet = meet && alo[d] <= bhi[d] && blo[d] <= ahi[d];
+        for (int d = 0; d < nd; d++) meet = meet && pa.lo[d] <= pb.hi[d] && pb.lo[d] <= pa.hi[d];
         if (meet) fatal("%s: overlapping patches of one array", what);   // npatch.c: "arrays overlap"
     }
     comex_barrier(COMEX_GROUP_WORLD);
     g_stat.numcopy++;
-    const Sub s = own_sub(a, alo, ahi);
-    if (s.any && !(g_a == g_b && same_patch(nd, alo, ahi, blo, bhi))) {
-        long dlo[GA_MAX_DIM], dhi[GA_MAX_DIM], ld[GA_MAX_DIM];
+    const Sub s = own_sub(a, pa);
+    if (s.any && !(g_a == g_b && same_patch(nd, pa, pb))) {
+        Patch dst;
+        long ld[GA_MAX_DIM];
         bool here = same_distr(a, b);
         for (int d = 0; d < nd; d++) {
-            dlo[d] = blo[d] + (s.plo[d] - alo[d]);
-            dhi[d] = dlo[d] + (s.phi[d] - s.plo[d]);
+            dst.lo[d] = pb.lo[d] + (s.plo[d] - pa.lo[d]);
+            dst.hi[d] = dst.lo[d] + (s.phi[d] - s.plo[d]);
             ld[d] = s.ext[d];
-            here = here && dlo[d] == s.plo[d];
+            here = here && dst.lo[d] == s.plo[d];
         }
         if (here) {
-            const Sub t = own_sub(b, dlo, dhi);
+            const Sub t = own_sub(b, dst);
             local_copy(s, t, nd, a.elemsize, what);
         } else {
-            patch_op(GA_PUT, g_b, dlo, dhi, s.p, ld, nullptr);
+            patch_op(GA_PUT, g_b, dst.lo, dst.hi, s.p, ld, nullptr);
         }
         g_stat.mathloc += 2 * s.bytes;
     }
     math_end(what);
 }
 
-static void add_patch(void *alpha, int g_a, const long *alo, const long *ahi, void *beta, int g_b, const long *blo,
-                      const long *bhi, int g_c, const long *clo, const long *chi, const char *what) {
-    int tmp[2] = {0, 0}, use[2] = {g_a, g_b};
-    {
-        GArray &a = arr(g_a), &b = arr(g_b), &c = arr(g_c);
-        if (a.type != c.type || b.type != c.type) fatal("%s: types of the arrays differ", what);
-        need_hbm(a, what);
-        need_hbm(b, what);
-        need_hbm(c, what);
-        check_patch(a, alo, ahi, what);
-        check_patch(b, blo, bhi, what);
-        check_patch(c, clo, chi, what);
-        need_same_shape(a, alo, ahi, c, clo, chi, what);
-        need_same_shape(b, blo, bhi, c, clo, chi, what);
-    }
+// RECIP / DIV: after the kernel has completed and math_end's barrier, the ranks combine
+// their zero-divisor flags; if any is set every rank ends here, none waits in a barrier
+static void zero_divisor_end(int flag, const char *what) {
+    char mx[] = "max";
+    armci_msg_igop(&flag, 1, mx);
+    if (flag)
+        fatal("%s: zero divisor (the reference aborts at the first one; here those elements were left unwritten)",
+              what);
+}
+
+// An input that does not lie on the target's block map and patch is first copied into a
+// GA_Duplicate of the target, as the reference does (npatch.c:2698-2737, 1207-1247).  The
+// temporaries of one call are destroyed, in the order they were made, when `Temps` goes
+// out of scope.
+struct Temps {
+    std::vector<int> made;
+    ~Temps() { for (int g : made) destroy(g); }
+};
+
+// the handle to compute with: g itself, or a temporary holding p at the target's patch
+static int on_map_of(int g, const Patch &p, int g_to, const Patch &pto, const char *tmp_name, Temps &temps,
+                     const char *what) {
+    if (same_distr(arr(g), arr(g_to)) && same_patch(arr(g_to).ndim, p, pto)) return g;
+    const int tmp = GA_Duplicate(g_to, const_cast<char *>(tmp_name));
+    temps.made.push_back(tmp);
+    copy_patch(g, p, tmp, pto, what);
+    return tmp;
+}
+
+// c = kernel(a, b) over patches of equal shape: GA_Add's structure (npatch.c) and
+// ngai_elem2_patch_'s (elem_alg.c:1851-1990), temporaries included.  `kernel` launches on
+// this rank's parts and returns its zero-divisor flag; combine_zero: the ranks combine it.
+typedef std::function<int(const GArray &c, const Sub &sa, const Sub &sb, const Sub &sc)> BinaryKernel;
+static void binary_patch(int g_a, const Patch &pa, int g_b, const Patch &pb, int g_c, const Patch &pc, long &counter,
+                         const char *tmp_name, bool combine_zero, const char *what, const BinaryKernel &kernel) {
+    const int g[3] = {g_a, g_b, g_c};
+    const Patch *p[3] = {&pa, &pb, &pc};
+    if (arr(g_a).type != arr(g_c).type || arr(g_b).type != arr(g_c).type) fatal("%s: types of the arrays differ", what);
+    for (int k = 0; k < 3; k++) need_hbm(arr(g[k]), what);
+    for (int k = 0; k < 3; k++) check_patch(arr(g[k]), *p[k], what);
+    for (int k = 0; k < 2; k++) need_same_shape(arr(g[k]), *p[k], arr(g_c), pc, what);
     comex_barrier(COMEX_GROUP_WORLD);
-    g_stat.numadd++;
-    const long *lo[2] = {alo, blo}, *hi[2] = {ahi, bhi};
-    for (int k = 0; k < 2; k++) {
-        const bool ok = same_distr(arr(use[k]), arr(g_c)) && same_patch(arr(g_c).ndim, lo[k], hi[k], clo, chi);
-        if (ok) continue;
-        char name[] = "ga_amd add temporary";
-        tmp[k] = GA_Duplicate(g_c, name);
-        copy_patch(use[k], lo[k], hi[k], tmp[k], clo, chi, what);
-        use[k] = tmp[k];
+    counter++;
+    int zero = 0;
+    {
+        Temps temps;
+        int use[2];
+        for (int k = 0; k < 2; k++) use[k] = on_map_of(g[k], *p[k], g_c, pc, tmp_name, temps, what);
+        GArray &c = arr(g_c);
+        const Sub sc = own_sub(c, pc);
+        if (sc.any) {
+            zero = kernel(c, own_sub(arr(use[0]), pc), own_sub(arr(use[1]), pc), sc);
+            g_stat.mathloc += 3 * sc.bytes;
+        }
+        math_end(what);
     }
-    GArray &c = arr(g_c);
-    const Sub sc = own_sub(c, clo, chi);
-    if (sc.any) {
-        const Sub sa = own_sub(arr(use[0]), clo, chi), sb = own_sub(arr(use[1]), clo, chi);
-        const int rc = gaamd_patch_add(c.optype, alpha, sa.p, sa.stride, beta, sb.p, sb.stride, sc.p, sc.stride,
-                                       sc.count, c.ndim, gaamd_stream());
-        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
-        g_stat.mathloc += 3 * sc.bytes;
-    }
-    math_end(what);
-    for (int k = 0; k < 2; k++)
-        if (tmp[k]) destroy(tmp[k]);
+    if (combine_zero) zero_divisor_end(zero, what);
 }
 
 // every rank returns the same bits: the local sums are combined by armci_msg_?gop
-static void dot_patch(int type, int g_a, char t_a, const long *alo, const long *ahi, int g_b, char t_b,
-                      const long *blo, const long *bhi, void *result, const char *what) {
-    int tmp = 0, use_b = g_b;
+static void dot_patch(int type, int g_a, char t_a, const Patch &pa, int g_b, char t_b, const Patch &pb, void *result,
+                      const char *what) {
     {
         GArray &a = arr(g_a), &b = arr(g_b);
         if (a.type != type || b.type != type)
@@ -1151,126 +1220,81 @@ static void dot_patch(int type, int g_a, char t_a, const long *alo, const long *
         need_no_trans(t_b, what);
         need_hbm(a, what);
         need_hbm(b, what);
-        check_patch(a, alo, ahi, what);
-        check_patch(b, blo, bhi, what);
-        need_same_shape(a, alo, ahi, b, blo, bhi, what);
+        check_patch(a, pa, what);
+        check_patch(b, pb, what);
+        need_same_shape(a, pa, b, pb, what);
     }
     comex_barrier(COMEX_GROUP_WORLD);
     g_stat.numdot++;
-    if (!(same_distr(arr(g_a), arr(g_b)) && same_patch(arr(g_a).ndim, alo, ahi, blo, bhi))) {
-        char name[] = "ga_amd dot temporary";
-        tmp = GA_Duplicate(g_a, name);
-        copy_patch(g_b, blo, bhi, tmp, alo, ahi, what);
-        use_b = tmp;
-    }
+    Temps temps;
+    const int use_b = on_map_of(g_b, pb, g_a, pa, "ga_amd dot temporary", temps, what);
     GArray &a = arr(g_a);
     double res[2] = {0.0, 0.0};   // 16 zero bytes: the zero of every type
-    const Sub sa = own_sub(a, alo, ahi);
+    const Sub sa = own_sub(a, pa);
     if (sa.any) {
-        const Sub sb = own_sub(arr(use_b), alo, ahi);
-        const int rc = gaamd_patch_dot(a.optype, sa.p, sa.stride, sb.p, sb.stride, sa.count, a.ndim, res,
-                                       gaamd_stream());
-        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        const Sub sb = own_sub(arr(use_b), pa);
+        launched(gaamd_patch_dot(a.optype, sa.p, sa.stride, sb.p, sb.stride, sa.count, a.ndim, res, gaamd_stream()), what);
         g_stat.mathloc += 2 * sa.bytes;
     }
     char plus[] = "+";
-    switch (type) {
-    case C_INT: armci_msg_igop((int *)res, 1, plus); break;
-    case C_LONG: armci_msg_lgop((long *)res, 1, plus); break;
-    case C_FLOAT: armci_msg_fgop((float *)res, 1, plus); break;
-    case C_DBL: armci_msg_dgop(res, 1, plus); break;
-    case C_SCPL: armci_msg_fgop((float *)res, 2, plus); break;
-    case C_DCPL: armci_msg_dgop(res, 2, plus); break;
-    }
+    const int parts = type == C_SCPL || type == C_DCPL ? 2 : 1;
+    gop_by_type(type, res, [&](auto *r, auto gop) { gop(r, parts, plus); });
     memcpy(result, res, (size_t)a.elemsize);
-    if (tmp) destroy(tmp);
 }
 
 void NGA_Fill_patch(int g_a, int lo[], int hi[], void *val) {
-    long flo[GA_MAX_DIM], fhi[GA_MAX_DIM];
-    c2f_index(arr(g_a).ndim, lo, flo);
-    c2f_index(arr(g_a).ndim, hi, fhi);
-    map_patch(M_FILL, g_a, flo, fhi, val, "NGA_Fill_patch");
+    map_patch(M_FILL, g_a, Patch(arr(g_a), lo, hi), val, "NGA_Fill_patch");
 }
 void NGA_Zero_patch(int g_a, int lo[], int hi[]) {
-    long flo[GA_MAX_DIM], fhi[GA_MAX_DIM];
     const double zero[2] = {0.0, 0.0};
-    c2f_index(arr(g_a).ndim, lo, flo);
-    c2f_index(arr(g_a).ndim, hi, fhi);
-    map_patch(M_FILL, g_a, flo, fhi, zero, "NGA_Zero_patch");
+    map_patch(M_FILL, g_a, Patch(arr(g_a), lo, hi), zero, "NGA_Zero_patch");
 }
 void NGA_Scale_patch(int g_a, int lo[], int hi[], void *alpha) {
-    long flo[GA_MAX_DIM], fhi[GA_MAX_DIM];
-    c2f_index(arr(g_a).ndim, lo, flo);
-    c2f_index(arr(g_a).ndim, hi, fhi);
-    map_patch(M_SCALE, g_a, flo, fhi, alpha, "NGA_Scale_patch");
+    map_patch(M_SCALE, g_a, Patch(arr(g_a), lo, hi), alpha, "NGA_Scale_patch");
 }
-void GA_Fill(int g_a, void *value) {
-    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
-    whole(arr(g_a), lo, hi);
-    map_patch(M_FILL, g_a, lo, hi, value, "GA_Fill");
-}
-void GA_Scale(int g_a, void *value) {
-    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
-    whole(arr(g_a), lo, hi);
-    map_patch(M_SCALE, g_a, lo, hi, value, "GA_Scale");
-}
+void GA_Fill(int g_a, void *value) { map_patch(M_FILL, g_a, Patch(arr(g_a), nullptr, nullptr), value, "GA_Fill"); }
+void GA_Scale(int g_a, void *value) { map_patch(M_SCALE, g_a, Patch(arr(g_a), nullptr, nullptr), value, "GA_Scale"); }
 
 void NGA_Copy_patch(char trans, int g_a, int alo[], int ahi[], int g_b, int blo[], int bhi[]) {
     need_no_trans(trans, "NGA_Copy_patch");
-    long fal[GA_MAX_DIM], fah[GA_MAX_DIM], fbl[GA_MAX_DIM], fbh[GA_MAX_DIM];
-    c2f_index(arr(g_a).ndim, alo, fal);
-    c2f_index(arr(g_a).ndim, ahi, fah);
-    c2f_index(arr(g_b).ndim, blo, fbl);
-    c2f_index(arr(g_b).ndim, bhi, fbh);
-    copy_patch(g_a, fal, fah, g_b, fbl, fbh, "NGA_Copy_patch");
+    const Patch pa(arr(g_a), alo, ahi), pb(arr(g_b), blo, bhi);
+    copy_patch(g_a, pa, g_b, pb, "NGA_Copy_patch");
 }
 void GA_Copy(int g_a, int g_b) {
-    long al[GA_MAX_DIM], ah[GA_MAX_DIM], bl[GA_MAX_DIM], bh[GA_MAX_DIM];
-    whole(arr(g_a), al, ah);
-    whole(arr(g_b), bl, bh);
-    copy_patch(g_a, al, ah, g_b, bl, bh, "GA_Copy");
+    const Patch pa(arr(g_a), nullptr, nullptr), pb(arr(g_b), nullptr, nullptr);
+    copy_patch(g_a, pa, g_b, pb, "GA_Copy");
 }
 
+// alo == nullptr: the whole arrays (GA_Add)
+static void c_add(void *alpha, int g_a, int *alo, int *ahi, void *beta, int g_b, int *blo, int *bhi, int g_c, int *clo,
+                  int *chi, const char *what) {
+    const Patch pa(arr(g_a), alo, ahi), pb(arr(g_b), blo, bhi), pc(arr(g_c), clo, chi);
+    binary_patch(g_a, pa, g_b, pb, g_c, pc, g_stat.numadd, "ga_amd add temporary", false, what,
+                 [&](const GArray &c, const Sub &sa, const Sub &sb, const Sub &sc) {
+                     return launched(gaamd_patch_add(c.optype, alpha, sa.p, sa.stride, beta, sb.p, sb.stride, sc.p,
+                                                     sc.stride, sc.count, c.ndim, gaamd_stream()),
+                                     what);
+                 });
+}
 void NGA_Add_patch(void *alpha, int g_a, int alo[], int ahi[], void *beta, int g_b, int blo[], int bhi[], int g_c,
                    int clo[], int chi[]) {
-    long l[3][GA_MAX_DIM], h[3][GA_MAX_DIM];
-    c2f_index(arr(g_a).ndim, alo, l[0]);
-    c2f_index(arr(g_a).ndim, ahi, h[0]);
-    c2f_index(arr(g_b).ndim, blo, l[1]);
-    c2f_index(arr(g_b).ndim, bhi, h[1]);
-    c2f_index(arr(g_c).ndim, clo, l[2]);
-    c2f_index(arr(g_c).ndim, chi, h[2]);
-    add_patch(alpha, g_a, l[0], h[0], beta, g_b, l[1], h[1], g_c, l[2], h[2], "NGA_Add_patch");
+    c_add(alpha, g_a, alo, ahi, beta, g_b, blo, bhi, g_c, clo, chi, "NGA_Add_patch");
 }
 void GA_Add(void *alpha, int g_a, void *beta, int g_b, int g_c) {
-    long l[3][GA_MAX_DIM], h[3][GA_MAX_DIM];
-    whole(arr(g_a), l[0], h[0]);
-    whole(arr(g_b), l[1], h[1]);
-    whole(arr(g_c), l[2], h[2]);
-    add_patch(alpha, g_a, l[0], h[0], beta, g_b, l[1], h[1], g_c, l[2], h[2], "GA_Add");
+    c_add(alpha, g_a, nullptr, nullptr, beta, g_b, nullptr, nullptr, g_c, nullptr, nullptr, "GA_Add");
 }
 
-static void c_dot_patch(int type, int g_a, char t_a, int alo[], int ahi[], int g_b, char t_b, int blo[], int bhi[],
+// alo == nullptr: the whole arrays (GA_?dot)
+static void c_dot_patch(int type, int g_a, char t_a, int *alo, int *ahi, int g_b, char t_b, int *blo, int *bhi,
                         void *res, const char *what) {
-    long fal[GA_MAX_DIM], fah[GA_MAX_DIM], fbl[GA_MAX_DIM], fbh[GA_MAX_DIM];
-    c2f_index(arr(g_a).ndim, alo, fal);
-    c2f_index(arr(g_a).ndim, ahi, fah);
-    c2f_index(arr(g_b).ndim, blo, fbl);
-    c2f_index(arr(g_b).ndim, bhi, fbh);
-    dot_patch(type, g_a, t_a, fal, fah, g_b, t_b, fbl, fbh, res, what);
-}
-static void c_dot(int type, int g_a, int g_b, void *res, const char *what) {
-    long al[GA_MAX_DIM], ah[GA_MAX_DIM], bl[GA_MAX_DIM], bh[GA_MAX_DIM];
-    whole(arr(g_a), al, ah);
-    whole(arr(g_b), bl, bh);
-    dot_patch(type, g_a, 'n', al, ah, g_b, 'n', bl, bh, res, what);
+    const Patch pa(arr(g_a), alo, ahi), pb(arr(g_b), blo, bhi);
+    dot_patch(type, g_a, t_a, pa, g_b, t_b, pb, res, what);
 }
 
 #define GAAMD_DOT(T, NAME, CODE)                                                                          \
     T GA_##NAME(int g_a, int g_b) {                                                                        \
         T v;                                                                                               \
-        c_dot(CODE, g_a, g_b, &v, "GA_" #NAME);                                                            \
+        c_dot_patch(CODE, g_a, 'n', nullptr, nullptr, g_b, 'n', nullptr, nullptr, &v, "GA_" #NAME);        \
         return v;                                                                                          \
     }                                                                                                      \
     T NGA_##NAME##_patch(int g_a, char t_a, int alo[], int ahi[], int g_b, char t_b, int blo[], int bhi[]) { \
@@ -1290,104 +1314,37 @@ GAAMD_DOT(DoubleComplex, Zdot, C_DCPL)
 // pnga_abs_value ... pnga_elem_minimum_patch (global/src/elem_alg.c) loop over the local
 // block on the host; here each rank runs gaamd_patch_elem1 / _elem2 on its part in HBM.
 
-// RECIP / DIV: after the kernel has completed and math_end's barrier, the ranks combine
-// their zero-divisor flags; if any is set every rank ends here, none waits in a barrier
-static void zero_divisor_end(int flag, const char *what) {
-    char mx[] = "max";
-    armci_msg_igop(&flag, 1, mx);
-    if (flag)
-        fatal("%s: zero divisor (the reference aborts at the first one; here those elements were left unwritten)",
-              what);
-}
-
-static void elem1_patch(int fn, int g_a, const long *lo, const long *hi, const void *alpha, const char *what) {
+static void elem1_patch(int fn, int g_a, const Patch &p, const void *alpha, const char *what) {
     GArray &a = arr(g_a);
     need_hbm(a, what);
-    check_patch(a, lo, hi, what);
+    check_patch(a, p, what);
     if (fn == GAAMD_ELEM_ADD_CONST && !alpha) fatal("%s: alpha is missing", what);
     comex_barrier(COMEX_GROUP_WORLD);   // fences every pending one-sided operation, then syncs
-    const Sub s = own_sub(a, lo, hi);
+    const Sub s = own_sub(a, p);
     g_stat.numelem[fn]++;
     int zero = 0;
     if (s.any) {
-        const int rc = gaamd_patch_elem1(a.optype, fn, alpha, s.p, s.stride, s.count, a.ndim, gaamd_stream());
-        if (rc == GAAMD_ZERO_DIVISOR) zero = 1;
-        else if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        zero = launched(gaamd_patch_elem1(a.optype, fn, alpha, s.p, s.stride, s.count, a.ndim, gaamd_stream()), what, true);
         g_stat.mathloc += 2 * s.bytes;
     }
     math_end(what);
     if (fn == GAAMD_ELEM_RECIP) zero_divisor_end(zero, what);
 }
 
-// ngai_elem2_patch_ (elem_alg.c:1851-1990): add_patch's structure, temporaries included
-static void elem2_patch(int fn, int g_a, const long *alo, const long *ahi, int g_b, const long *blo, const long *bhi,
-                        int g_c, const long *clo, const long *chi, const char *what) {
-    int tmp[2] = {0, 0}, use[2] = {g_a, g_b};
-    {
-        GArray &a = arr(g_a), &b = arr(g_b), &c = arr(g_c);
-        if (a.type != c.type || b.type != c.type) fatal("%s: types of the arrays differ", what);
-        need_hbm(a, what);
-        need_hbm(b, what);
-        need_hbm(c, what);
-        check_patch(a, alo, ahi, what);
-        check_patch(b, blo, bhi, what);
-        check_patch(c, clo, chi, what);
-        need_same_shape(a, alo, ahi, c, clo, chi, what);
-        need_same_shape(b, blo, bhi, c, clo, chi, what);
-    }
-    comex_barrier(COMEX_GROUP_WORLD);
-    g_stat.numelem[fn]++;
-    const long *lo[2] = {alo, blo}, *hi[2] = {ahi, bhi};
-    for (int k = 0; k < 2; k++) {
-        const bool ok = same_distr(arr(use[k]), arr(g_c)) && same_patch(arr(g_c).ndim, lo[k], hi[k], clo, chi);
-        if (ok) continue;
-        char name[] = "ga_amd elem temporary";
-        tmp[k] = GA_Duplicate(g_c, name);
-        copy_patch(use[k], lo[k], hi[k], tmp[k], clo, chi, what);
-        use[k] = tmp[k];
-    }
-    GArray &c = arr(g_c);
-    const Sub sc = own_sub(c, clo, chi);
-    int zero = 0;
-    if (sc.any) {
-        const Sub sa = own_sub(arr(use[0]), clo, chi), sb = own_sub(arr(use[1]), clo, chi);
-        const int rc = gaamd_patch_elem2(c.optype, fn, sa.p, sa.stride, sb.p, sb.stride, sc.p, sc.stride, sc.count,
-                                         c.ndim, gaamd_stream());
-        if (rc == GAAMD_ZERO_DIVISOR) zero = 1;
-        else if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
-        g_stat.mathloc += 3 * sc.bytes;
-    }
-    math_end(what);
-    for (int k = 0; k < 2; k++)
-        if (tmp[k]) destroy(tmp[k]);
-    if (fn == GAAMD_ELEM_DIV) zero_divisor_end(zero, what);
-}
-
+// lo == nullptr: the whole array
 static void c_elem1(int fn, int g_a, int *lo, int *hi, const void *alpha, const char *what) {
-    long flo[GA_MAX_DIM], fhi[GA_MAX_DIM];
-    if (lo) {
-        c2f_index(arr(g_a).ndim, lo, flo);
-        c2f_index(arr(g_a).ndim, hi, fhi);
-    } else {
-        whole(arr(g_a), flo, fhi);
-    }
-    elem1_patch(fn, g_a, flo, fhi, alpha, what);
+    elem1_patch(fn, g_a, Patch(arr(g_a), lo, hi), alpha, what);
 }
 
 static void c_elem2(int fn, int g_a, int *alo, int *ahi, int g_b, int *blo, int *bhi, int g_c, int *clo, int *chi,
                     const char *what) {
-    long l[3][GA_MAX_DIM], h[3][GA_MAX_DIM];
-    const int g[3] = {g_a, g_b, g_c};
-    int *const lo[3] = {alo, blo, clo}, *const hi[3] = {ahi, bhi, chi};
-    for (int k = 0; k < 3; k++) {
-        if (lo[k]) {
-            c2f_index(arr(g[k]).ndim, lo[k], l[k]);
-            c2f_index(arr(g[k]).ndim, hi[k], h[k]);
-        } else {
-            whole(arr(g[k]), l[k], h[k]);
-        }
-    }
-    elem2_patch(fn, g_a, l[0], h[0], g_b, l[1], h[1], g_c, l[2], h[2], what);
+    const Patch pa(arr(g_a), alo, ahi), pb(arr(g_b), blo, bhi), pc(arr(g_c), clo, chi);
+    binary_patch(g_a, pa, g_b, pb, g_c, pc, g_stat.numelem[fn], "ga_amd elem temporary", fn == GAAMD_ELEM_DIV, what,
+                 [&](const GArray &c, const Sub &sa, const Sub &sb, const Sub &sc) {
+                     return launched(gaamd_patch_elem2(c.optype, fn, sa.p, sa.stride, sb.p, sb.stride, sc.p, sc.stride,
+                                                       sc.count, c.ndim, gaamd_stream()),
+                                     what, true);
+                 });
 }
 
 void GA_Abs_value(int g_a) { c_elem1(GAAMD_ELEM_ABS, g_a, nullptr, nullptr, nullptr, "GA_Abs_value"); }
@@ -1430,18 +1387,15 @@ void NGA_Select_elem(int g_a, char *op, void *val, int *index) {
     const bool mx = strncmp(op, "max", 3) == 0;
     comex_barrier(COMEX_GROUP_WORLD);
     g_stat.numselect++;
-    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
-    whole(a, lo, hi);
-    const Sub s = own_sub(a, lo, hi);
+    const Sub s = own_sub(a, Patch(a, nullptr, nullptr));
     int bits[4] = {0, 0, 0, 0};
-    union { int i; long l; float f; double d; } key, best;
+    union { int i; long l; float f; double d; } key;
     memset(&key, 0, sizeof(key));
     long lin = 0;
     if (s.any) {
         long long li = -1;
-        const int rc = gaamd_patch_select(a.optype, mx ? 1 : 0, s.p, s.stride, s.count, a.ndim, bits, &key, &li,
-                                          gaamd_stream());
-        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        launched(gaamd_patch_select(a.optype, mx ? 1 : 0, s.p, s.stride, s.count, a.ndim, bits, &key, &li, gaamd_stream()),
+                 what);
         long mult = 1;
         for (int d = 0; d < a.ndim; d++) {   // block-local, dimension 0 fastest -> whole array
             lin += (s.plo[d] - 1 + (long)(li % s.count[d])) * mult;
@@ -1454,29 +1408,13 @@ void NGA_Select_elem(int g_a, char *op, void *val, int *index) {
     char opname[4];
     snprintf(opname, sizeof(opname), "%s", mx ? "max" : "min");
     bool holder = s.any;
-    switch (a.type) {
-    case C_INT:
-        best.i = s.any ? key.i : (mx ? INT_MIN : INT_MAX);
-        armci_msg_igop(&best.i, 1, opname);
-        holder = holder && key.i == best.i;
-        break;
-    case C_LONG:
-        best.l = s.any ? key.l : (mx ? LONG_MIN : LONG_MAX);
-        armci_msg_lgop(&best.l, 1, opname);
-        holder = holder && key.l == best.l;
-        break;
-    case C_FLOAT:
-    case C_SCPL:
-        best.f = s.any ? key.f : (mx ? -HUGE_VALF : HUGE_VALF);
-        armci_msg_fgop(&best.f, 1, opname);
-        holder = holder && key.f == best.f;
-        break;
-    default:
-        best.d = s.any ? key.d : (mx ? -HUGE_VAL : HUGE_VAL);
-        armci_msg_dgop(&best.d, 1, opname);
-        holder = holder && key.d == best.d;
-        break;
-    }
+    gop_by_type(a.type, &key, [&](auto *k, auto gop) {
+        typedef std::numeric_limits<std::remove_pointer_t<decltype(k)>> L;   // identity: the type's end, or infinity
+        auto best = s.any ? *k : mx ? (L::has_infinity ? -L::infinity() : L::lowest())
+                                    : (L::has_infinity ? L::infinity() : L::max());
+        gop(&best, 1, opname);
+        holder = holder && *k == best;
+    });
     char mn[] = "min", plus[] = "+";
     long first = holder ? lin : LONG_MAX;
     armci_msg_lgop(&first, 1, mn);
@@ -1513,15 +1451,14 @@ static bool is_trans(char t, const char *what, bool cplx) {
     fatal("%s: trans '%c' is not one of N n T t", what, t);
 }
 
-static bool patches_meet(const long *alo, const long *ahi, const long *blo, const long *bhi) {
-    return alo[0] <= bhi[0] && blo[0] <= ahi[0] && alo[1] <= bhi[1] && blo[1] <= ahi[1];
+static bool patches_meet(const Patch &a, const Patch &b) {
+    return a.lo[0] <= b.hi[0] && b.lo[0] <= a.hi[0] && a.lo[1] <= b.hi[1] && b.lo[1] <= a.hi[1];
 }
 
 // patches in Fortran order, 1-based: index 0 runs along a stored row (the C column
 // subscript), index 1 down the rows.  type: the array type the call is for, 0 = either.
 static void matmul_patch(int type, char transa, char transb, const void *alpha, const void *beta, int g_a,
-                         const long *alo, const long *ahi, int g_b, const long *blo, const long *bhi, int g_c,
-                         const long *clo, const long *chi, const char *what) {
+                         const Patch &pa, int g_b, const Patch &pb, int g_c, const Patch &pc, const char *what) {
     GArray &a = arr(g_a), &b = arr(g_b), &c = arr(g_c);
     const bool cplx = c.type == C_DCPL || c.type == C_SCPL;
     const bool ta = is_trans(transa, what, cplx), tb = is_trans(transb, what, cplx);
@@ -1532,31 +1469,31 @@ static void matmul_patch(int type, char transa, char transb, const void *alpha, 
         fatal("%s: type mismatch: arrays of type %d in a call for type %d", what, c.type, type);
     if (a.ndim != 2 || b.ndim != 2 || c.ndim != 2) fatal("%s: arrays of rank other than 2 are not supported", what);
     if (!alpha || !beta) fatal("%s: alpha or beta is missing", what);
-    need_hbm(a, what);
-    need_hbm(b, what);
-    need_hbm(c, what);
-    check_patch(a, alo, ahi, what);
-    check_patch(b, blo, bhi, what);
-    check_patch(c, clo, chi, what);
+    const GArray *const abc[3] = {&a, &b, &c};
+    const Patch *const pabc[3] = {&pa, &pb, &pc};
+    for (int i = 0; i < 3; i++) need_hbm(*abc[i], what);
+    for (int i = 0; i < 3; i++) check_patch(*abc[i], *pabc[i], what);
     // op(A) is m x k, op(B) is k x n, C is m x n (matmul.c:1376-1381)
-    const long arows = ahi[1] - alo[1] + 1, acols = ahi[0] - alo[0] + 1;
-    const long brows = bhi[1] - blo[1] + 1, bcols = bhi[0] - blo[0] + 1;
+    const long arows = pa.hi[1] - pa.lo[1] + 1, acols = pa.hi[0] - pa.lo[0] + 1;
+    const long brows = pb.hi[1] - pb.lo[1] + 1, bcols = pb.hi[0] - pb.lo[0] + 1;
     const long m = ta ? acols : arows, k = ta ? arows : acols, kb = tb ? bcols : brows, n = tb ? brows : bcols;
-    if (kb != k || chi[1] - clo[1] + 1 != m || chi[0] - clo[0] + 1 != n)
+    if (kb != k || pc.hi[1] - pc.lo[1] + 1 != m || pc.hi[0] - pc.lo[0] + 1 != n)
         fatal("%s: patch extents do not agree: op(A) is %ld x %ld, op(B) %ld x %ld, C %ld x %ld", what, m, k, kb, n,
-              chi[1] - clo[1] + 1, chi[0] - clo[0] + 1);
+              pc.hi[1] - pc.lo[1] + 1, pc.hi[0] - pc.lo[0] + 1);
     // every owner writes its part of C while others still read A and B
-    if ((g_c == g_a && patches_meet(clo, chi, alo, ahi)) || (g_c == g_b && patches_meet(clo, chi, blo, bhi)))
+    if ((g_c == g_a && patches_meet(pc, pa)) || (g_c == g_b && patches_meet(pc, pb)))
         fatal("%s: the C patch overlaps an input patch of the same array", what);
     comex_barrier(COMEX_GROUP_WORLD);
     g_stat.numgemm++;
-    const Sub sc = own_sub(c, clo, chi);
+    const Sub sc = own_sub(c, pc);
     if (sc.any) {
         const long mi = (long)sc.count[1], nj = (long)sc.count[0];       // this rank's rows and columns of C
-        const long i0 = sc.plo[1] - clo[1], j0 = sc.plo[0] - clo[0];     // ... from the patch's corner
+        const long i0 = sc.plo[1] - pc.lo[1], j0 = sc.plo[0] - pc.lo[0];     // ... from the patch's corner
         const long kmax = std::min(k, kGemmPanel);
-        void *pa = gaamd_dev_malloc((size_t)mi * kmax * c.elemsize), *pb = gaamd_dev_malloc((size_t)kmax * nj * c.elemsize);
-        if (!pa || !pb) fatal("%s: no device memory for the panel buffers", what);
+        Scratch bufa, bufb;
+        bufa.alloc((size_t)mi * kmax * c.elemsize);
+        bufb.alloc((size_t)kmax * nj * c.elemsize);
+        if (!bufa.p || !bufb.p) fatal("%s: no device memory for the panel buffers", what);
         const double one_d[2] = {1.0, 0.0};   // 1, or (1,0) for the complex types
         const float one_f[2] = {1.0f, 0.0f};
         const void *one = c.type == C_DBL || c.type == C_DCPL ? (const void *)one_d : (const void *)one_f;
@@ -1564,28 +1501,25 @@ static void matmul_patch(int type, char transa, char transb, const void *alpha, 
             const long kl = std::min(kGemmPanel, k - kp);
             long lo[2], hi[2], ld[1];
             // rows i0 .. i0 + mi of op(A), columns kp .. kp + kl: stored mi x kl, or kl x mi for 'T'
-            lo[0] = alo[0] + (ta ? i0 : kp);
+            lo[0] = pa.lo[0] + (ta ? i0 : kp);
             hi[0] = lo[0] + (ta ? mi : kl) - 1;
-            lo[1] = alo[1] + (ta ? kp : i0);
+            lo[1] = pa.lo[1] + (ta ? kp : i0);
             hi[1] = lo[1] + (ta ? kl : mi) - 1;
             const long lda = ld[0] = hi[0] - lo[0] + 1;
-            patch_op(GA_GET, g_a, lo, hi, pa, ld, nullptr);
+            patch_op(GA_GET, g_a, lo, hi, bufa.p, ld, nullptr);
             // rows kp .. kp + kl of op(B), columns j0 .. j0 + nj: stored kl x nj, or nj x kl for 'T'
-            lo[0] = blo[0] + (tb ? kp : j0);
+            lo[0] = pb.lo[0] + (tb ? kp : j0);
             hi[0] = lo[0] + (tb ? kl : nj) - 1;
-            lo[1] = blo[1] + (tb ? j0 : kp);
+            lo[1] = pb.lo[1] + (tb ? j0 : kp);
             hi[1] = lo[1] + (tb ? nj : kl) - 1;
             const long ldb = ld[0] = hi[0] - lo[0] + 1;
-            patch_op(GA_GET, g_b, lo, hi, pb, ld, nullptr);
-            const int rc = (cplx ? gaamd_gemm_cplx : gaamd_gemm)(c.optype, transa, transb, mi, nj, kl, alpha, pa, lda, pb,
-                                                                 ldb, kp ? one : beta, sc.p, sc.ext[0], gaamd_stream());
-            if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
-            // the next panel's gets overwrite the buffers
-            if (gaamd_sync(gaamd_stream()) != 0) fatal("%s: the stream failed", what);
+            patch_op(GA_GET, g_b, lo, hi, bufb.p, ld, nullptr);
+            launched((cplx ? gaamd_gemm_cplx : gaamd_gemm)(c.optype, transa, transb, mi, nj, kl, alpha, bufa.p, lda, bufb.p,
+                                                           ldb, kp ? one : beta, sc.p, sc.ext[0], gaamd_stream()),
+                     what);
+            stream_wait(what);   // the next panel's gets overwrite the buffers
             g_stat.mathloc += (double)c.elemsize * ((double)mi * kl + (double)kl * nj + 2.0 * mi * nj);
         }
-        gaamd_dev_free(pa);
-        gaamd_dev_free(pb);
     }
     math_end(what);
 }
@@ -1595,9 +1529,15 @@ static void c_gemm(int type, char ta, char tb, int m, int n, int k, const void *
     // the leading corners, as stored: A m x k (k x m for 'T'), B k x n (n x k), C m x n
     const bool cplx = type == C_DCPL || type == C_SCPL;
     const bool tra = is_trans(ta, what, cplx), trb = is_trans(tb, what, cplx);
-    const long one[2] = {1, 1};
-    const long ah[2] = {tra ? m : k, tra ? k : m}, bh[2] = {trb ? k : n, trb ? n : k}, ch[2] = {n, m};
-    matmul_patch(type, ta, tb, alpha, beta, g_a, one, ah, g_b, one, bh, g_c, one, ch, what);
+    const auto corner = [](long cols, long rows) {
+        Patch p;
+        p.lo[0] = p.lo[1] = 1;
+        p.hi[0] = cols;
+        p.hi[1] = rows;
+        return p;
+    };
+    matmul_patch(type, ta, tb, alpha, beta, g_a, corner(tra ? m : k, tra ? k : m), g_b, corner(trb ? k : n, trb ? n : k),
+                 g_c, corner(n, m), what);
 }
 
 void GA_Dgemm(char ta, char tb, int m, int n, int k, double alpha, int g_a, int g_b, double beta, int g_c) {
@@ -1616,15 +1556,14 @@ void GA_Cgemm(char ta, char tb, int m, int n, int k, SingleComplex alpha, int g_
 }
 void NGA_Matmul_patch(char transa, char transb, void *alpha, void *beta, int g_a, int alo[], int ahi[], int g_b,
                       int blo[], int bhi[], int g_c, int clo[], int chi[]) {
-    long l[3][GA_MAX_DIM], h[3][GA_MAX_DIM];
     const int g[3] = {g_a, g_b, g_c};
     int *lo[3] = {alo, blo, clo}, *hi[3] = {ahi, bhi, chi};
+    Patch p[3];
     for (int i = 0; i < 3; i++) {
         if (arr(g[i]).ndim != 2) fatal("NGA_Matmul_patch: arrays of rank other than 2 are not supported");
-        c2f_index(2, lo[i], l[i]);
-        c2f_index(2, hi[i], h[i]);
+        p[i] = Patch(arr(g[i]), lo[i], hi[i]);
     }
-    matmul_patch(0, transa, transb, alpha, beta, g_a, l[0], h[0], g_b, l[1], h[1], g_c, l[2], h[2], "NGA_Matmul_patch");
+    matmul_patch(0, transa, transb, alpha, beta, g_a, p[0], g_b, p[1], g_c, p[2], "NGA_Matmul_patch");
 }
 int gaamd_ga_gemm_panel(void) { return (int)kGemmPanel; }
 
@@ -1639,11 +1578,12 @@ int gaamd_ga_gemm_panel(void) { return (int)kGemmPanel; }
 
 // the mirror of this rank's part `s` of a 2-D array, fetched from g_src into new scratch:
 // stored count[0] x count[1] with ld = count[1]
-static void *get_mirror(int g_src, const GArray &dst, const Sub &s, const char *what) {
-    void *buf = gaamd_dev_malloc((size_t)s.count[0] * (size_t)s.count[1] * dst.elemsize);
-    if (!buf) fatal("%s: no device memory for the %lld x %lld scratch block", what, s.count[0], s.count[1]);
+static Scratch get_mirror(int g_src, const GArray &dst, const Sub &s, const char *what) {
+    Scratch buf;
+    if (!buf.alloc((size_t)s.count[0] * (size_t)s.count[1] * dst.elemsize))
+        fatal("%s: no device memory for the %lld x %lld scratch block", what, s.count[0], s.count[1]);
     const long lo[2] = {s.plo[1], s.plo[0]}, hi[2] = {s.phi[1], s.phi[0]}, ld[1] = {(long)s.count[1]};
-    patch_op(GA_GET, g_src, lo, hi, buf, ld, nullptr);
+    patch_op(GA_GET, g_src, lo, hi, buf.p, ld, nullptr);
     return buf;
 }
 
@@ -1660,21 +1600,21 @@ void GA_Transpose(int g_a, int g_b) {
     need_hbm(b, what);
     comex_barrier(COMEX_GROUP_WORLD);
     g_stat.numtranspose++;
-    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
-    whole(b, lo, hi);
-    const Sub s = own_sub(b, lo, hi);
+    const Sub s = own_sub(b, Patch(b, nullptr, nullptr));
     if (s.any) {
         // the block is count[1] rows of count[0]; its mirror in A is count[0] rows of count[1].
         // A mirror that lies wholly in this rank's own block of A is read there, without a get.
-        const long mlo[2] = {s.plo[1], s.plo[0]}, mhi[2] = {s.phi[1], s.phi[0]};
-        const Sub sa = own_sub(a, mlo, mhi);
+        Patch mirror;
+        for (int d = 0; d < 2; d++) { mirror.lo[d] = s.plo[1 - d]; mirror.hi[d] = s.phi[1 - d]; }
+        const Sub sa = own_sub(a, mirror);
         const bool own = sa.any && sa.count[0] == s.count[1] && sa.count[1] == s.count[0];
-        void *buf = own ? nullptr : get_mirror(g_a, b, s, what);
-        const int rc = gaamd_transpose(b.optype, s.count[0], s.count[1], own ? sa.p : buf, own ? sa.ext[0] : s.count[1],
-                                       s.p, s.ext[0], gaamd_stream());
-        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
-        if (gaamd_sync(gaamd_stream()) != 0) fatal("%s: the stream failed", what);
-        if (buf) gaamd_dev_free(buf);
+        Scratch buf;
+        if (!own) buf = get_mirror(g_a, b, s, what);
+        launched(gaamd_transpose(b.optype, s.count[0], s.count[1], own ? sa.p : buf.p, own ? sa.ext[0] : s.count[1], s.p,
+                                 s.ext[0], gaamd_stream()),
+                 what);
+        stream_wait(what);
+        buf.free();
         g_stat.mathloc += 2 * s.bytes;
     }
     math_end(what);
@@ -1689,23 +1629,22 @@ void GA_Symmetrize(int g_a) {
     need_hbm(a, what);
     comex_barrier(COMEX_GROUP_WORLD);
     g_stat.numsymm++;
-    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
-    whole(a, lo, hi);
-    const Sub s = own_sub(a, lo, hi);
+    const Sub s = own_sub(a, Patch(a, nullptr, nullptr));
     // always through the scratch copy, on one rank too: in place, a block on the diagonal
     // would read what it is writing
-    void *buf = s.any ? get_mirror(g_a, a, s, what) : nullptr;
-    if (gaamd_sync(gaamd_stream()) != 0) fatal("%s: the stream failed", what);
+    Scratch buf;
+    if (s.any) buf = get_mirror(g_a, a, s, what);
+    stream_wait(what);
     comex_barrier(COMEX_GROUP_WORLD);   // every rank has read before any rank writes (ga_symmetr.c:105)
     if (s.any) {
         const double half_d = 0.5;
         const float half_f = 0.5f;
         const void *half = a.type == C_DBL ? (const void *)&half_d : (const void *)&half_f;
-        const int rc = gaamd_transpose_acc(a.optype, s.count[1], s.count[0], half, buf, s.count[1], s.p, s.ext[0],
-                                           gaamd_stream());
-        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
-        if (gaamd_sync(gaamd_stream()) != 0) fatal("%s: the stream failed", what);
-        gaamd_dev_free(buf);
+        launched(gaamd_transpose_acc(a.optype, s.count[1], s.count[0], half, buf.p, s.count[1], s.p, s.ext[0],
+                                     gaamd_stream()),
+                 what);
+        stream_wait(what);
+        buf.free();
         g_stat.mathloc += 3 * s.bytes;
     }
     math_end(what);
@@ -1723,17 +1662,18 @@ enum VecUse { V_NONE, V_READ, V_WRITE };
 // elements [lo, hi] (1-based) of the 1-D array g_v for this rank's kernel: its own block in
 // place, or scratch (filled by a get for V_READ)
 struct VecPart {
-    void *p = nullptr, *scratch = nullptr;
+    void *p = nullptr;
+    Scratch scratch;
 };
 static VecPart vec_part(int g_v, long lo, long hi, VecUse use, const char *what) {
     VecPart r;
     GArray &v = arr(g_v);
-    const Sub sv = own_sub(v, &lo, &hi);
+    const Sub sv = own_sub(v, Patch(lo, hi));
     if (sv.any && sv.count[0] == hi - lo + 1) {
         r.p = sv.p;
         return r;
     }
-    r.p = r.scratch = gaamd_dev_malloc((size_t)(hi - lo + 1) * v.elemsize);
+    r.p = r.scratch.alloc((size_t)(hi - lo + 1) * v.elemsize);
     if (!r.p) fatal("%s: no device memory for %ld elements of scratch", what, hi - lo + 1);
     const long ld[1] = {0};
     if (use == V_READ) patch_op(GA_GET, g_v, &lo, &hi, r.p, ld, nullptr);
@@ -1742,15 +1682,14 @@ static VecPart vec_part(int g_v, long lo, long hi, VecUse use, const char *what)
 
 // the kernel has written the scratch: store it into g_v, complete at its owner, and free it
 static void vec_done(int g_v, long lo, long hi, VecPart &r, VecUse use, const char *what) {
-    if (gaamd_sync(gaamd_stream()) != 0) fatal("%s: the stream failed", what);
-    if (!r.scratch) return;
+    stream_wait(what);
+    if (!r.scratch.p) return;
     if (use == V_WRITE) {
         const long ld[1] = {0};
-        patch_op(GA_PUT, g_v, &lo, &hi, r.scratch, ld, nullptr);
+        patch_op(GA_PUT, g_v, &lo, &hi, r.scratch.p, ld, nullptr);
         comex_fence_all(COMEX_GROUP_WORLD);
     }
-    gaamd_dev_free(r.scratch);
-    r.scratch = nullptr;
+    r.scratch.free();
 }
 
 static void need_vector(const GArray &a, int g_v, long len, const char *what) {
@@ -1770,9 +1709,7 @@ static void diagonal_call(int fn, int g_a, int g_v, const void *c, const char *w
     if (fn == GAAMD_DIAG_SHIFT && !c) fatal("%s: the constant is missing", what);
     comex_barrier(COMEX_GROUP_WORLD);
     g_stat.numdiag++;
-    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
-    whole(a, lo, hi);
-    const Sub s = own_sub(a, lo, hi);
+    const Sub s = own_sub(a, Patch(a, nullptr, nullptr));
     // rows plo[1]..phi[1], columns plo[0]..phi[0]: the diagonal elements d0..d1 (1-based)
     const long d0 = s.any ? std::max(s.plo[0], s.plo[1]) : 1, d1 = s.any ? std::min(s.phi[0], s.phi[1]) : 0;
     if (d0 <= d1) {
@@ -1780,9 +1717,9 @@ static void diagonal_call(int fn, int g_a, int g_v, const void *c, const char *w
         char *p = s.p + ((d0 - s.plo[1]) * s.ext[0] + (d0 - s.plo[0])) * a.elemsize;
         VecPart v;
         if (use != V_NONE) v = vec_part(g_v, d0, d1, use, what);
-        const int rc = gaamd_diagonal(a.optype, fn, n, p, (long long)(s.ext[0] + 1) * a.elemsize, v.p, a.elemsize, c,
-                                      gaamd_stream());
-        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        launched(gaamd_diagonal(a.optype, fn, n, p, (long long)(s.ext[0] + 1) * a.elemsize, v.p, a.elemsize, c,
+                                gaamd_stream()),
+                 what);
         vec_done(g_v, d0, d1, v, use, what);
         g_stat.mathloc += (double)n * a.elemsize * (use == V_NONE && fn == GAAMD_DIAG_ZERO ? 1 : 2);
     }
@@ -1798,14 +1735,12 @@ static void scale_rc_call(bool rows, int g_a, int g_v, const char *what) {
     need_vector(a, g_v, a.dims[dim], what);
     comex_barrier(COMEX_GROUP_WORLD);
     (rows ? g_stat.numscalerows : g_stat.numscalecols)++;
-    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
-    whole(a, lo, hi);
-    const Sub s = own_sub(a, lo, hi);
+    const Sub s = own_sub(a, Patch(a, nullptr, nullptr));
     if (s.any) {
         VecPart v = vec_part(g_v, s.plo[dim], s.phi[dim], V_READ, what);
-        const int rc = rows ? gaamd_scale_rows(a.optype, s.count[1], s.count[0], s.p, s.ext[0], v.p, gaamd_stream())
-                            : gaamd_scale_cols(a.optype, s.count[1], s.count[0], s.p, s.ext[0], v.p, gaamd_stream());
-        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        launched(rows ? gaamd_scale_rows(a.optype, s.count[1], s.count[0], s.p, s.ext[0], v.p, gaamd_stream())
+                      : gaamd_scale_cols(a.optype, s.count[1], s.count[0], s.p, s.ext[0], v.p, gaamd_stream()),
+                 what);
         vec_done(g_v, s.plo[dim], s.phi[dim], v, V_READ, what);
         g_stat.mathloc += 2 * s.bytes;
     }
@@ -1821,25 +1756,19 @@ static void norm_call(int kind, int g_a, double *nm, const char *what) {
     need_hbm(a, what);
     comex_barrier(COMEX_GROUP_WORLD);
     (kind == GAAMD_NORM_ONE ? g_stat.numnorm1 : g_stat.numnorminf)++;
-    long lo[GA_MAX_DIM], hi[GA_MAX_DIM];
-    whole(a, lo, hi);
-    const Sub s = own_sub(a, lo, hi);
+    const Sub s = own_sub(a, Patch(a, nullptr, nullptr));
     union { int i; long l; float f; double d; } res;
     memset(&res, 0, sizeof(res));   // a rank owning nothing contributes 0
     if (s.any) {
-        const int rc = gaamd_patch_norm(a.optype, kind, s.p, s.stride, s.count, a.ndim, &res, gaamd_stream());
-        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        launched(gaamd_patch_norm(a.optype, kind, s.p, s.stride, s.count, a.ndim, &res, gaamd_stream()), what);
         g_stat.mathloc += s.bytes;
     }
     char opname[4];
     snprintf(opname, sizeof(opname), "%s", kind == GAAMD_NORM_ONE ? "+" : "max");
-    switch (a.type) {
-    case C_INT: armci_msg_igop(&res.i, 1, opname); *nm = (double)res.i; break;
-    case C_LONG: armci_msg_lgop(&res.l, 1, opname); *nm = (double)res.l; break;
-    case C_FLOAT:
-    case C_SCPL: armci_msg_fgop(&res.f, 1, opname); *nm = (double)res.f; break;
-    default: armci_msg_dgop(&res.d, 1, opname); *nm = res.d; break;
-    }
+    gop_by_type(a.type, &res, [&](auto *r, auto gop) {
+        gop(r, 1, opname);
+        *nm = (double)*r;
+    });
     comex_barrier(COMEX_GROUP_WORLD);
 }
 
@@ -1908,10 +1837,9 @@ static void enum_call(int g_a, long lo, long hi, const void *start, const void *
     if (!start || !inc) fatal("%s: the start or the increment is missing", what);
     comex_barrier(COMEX_GROUP_WORLD);
     g_stat.numenum++;
-    const Sub s = own_sub(a, &lo, &hi);
+    const Sub s = own_sub(a, Patch(lo, hi));
     if (s.any) {
-        const int rc = gaamd_enum(a.optype, s.count[0], s.plo[0] - lo, start, inc, s.p, gaamd_stream());
-        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        launched(gaamd_enum(a.optype, s.count[0], s.plo[0] - lo, start, inc, s.p, gaamd_stream()), what);
         g_stat.mathloc += s.bytes;
     }
     math_end(what);
@@ -1930,14 +1858,14 @@ static void scan_call(int fn, int g_src, int g_dst, int g_msk, long lo, long hi,
     comex_barrier(COMEX_GROUP_WORLD);
     (fn == GAAMD_SCAN_COPY ? g_stat.numscancopy : g_stat.numscanadd)++;
     const int me = my_rank(), np = world_size();
-    const Sub ss = own_sub(src, &lo, &hi), sd = own_sub(dst, &lo, &hi), sm = own_sub(msk, &lo, &hi);
+    const Patch range(lo, hi);
+    const Sub ss = own_sub(src, range), sd = own_sub(dst, range), sm = own_sub(msk, range);
     // slot r: {1 rank r has a part of the range | 2 it holds a set element, its tail (16 bytes)}
     std::vector<long> slots((size_t)np * 3, 0);
     if (sm.any) {
         int flag = 0;
         long tail[2] = {0, 0};
-        const int rc = gaamd_scan_tail(src.optype, fn, msk.optype, sm.count[0], ss.p, sm.p, &flag, tail, gaamd_stream());
-        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        launched(gaamd_scan_tail(src.optype, fn, msk.optype, sm.count[0], ss.p, sm.p, &flag, tail, gaamd_stream()), what);
         slots[(size_t)me * 3] = 1 | (flag ? 2 : 0);
         slots[(size_t)me * 3 + 1] = tail[0];
         slots[(size_t)me * 3 + 2] = tail[1];
@@ -1955,9 +1883,9 @@ static void scan_call(int fn, int g_src, int g_dst, int g_msk, long lo, long hi,
                 for (int r = from + 1; r < me; r++)
                     if (slots[(size_t)r * 3] & 1) host_add(src.type, carry, &slots[(size_t)r * 3 + 1]);
         }
-        const int rc = gaamd_scan(src.optype, fn, msk.optype, sm.count[0], ss.p, sm.p, sd.p, from >= 0 ? 1 : 0, carry,
-                                  gaamd_stream());
-        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        launched(gaamd_scan(src.optype, fn, msk.optype, sm.count[0], ss.p, sm.p, sd.p, from >= 0 ? 1 : 0, carry,
+                            gaamd_stream()),
+                 what);
         g_stat.mathloc += 3 * ss.bytes + 2 * sm.bytes;   // src twice and dst, msk twice
     }
     math_end(what);
@@ -1974,7 +1902,7 @@ static VecPart packed_part(int g_b, long place, long cnt, long n, bool read, con
         r.p = (char *)b.ptr[my_rank()] + (lo - blo[0]) * b.elemsize;
         return r;
     }
-    r.p = r.scratch = gaamd_dev_malloc((size_t)n * b.elemsize);
+    r.p = r.scratch.alloc((size_t)n * b.elemsize);
     if (!r.p) fatal("%s: no device memory for %ld elements of scratch", what, n);
     const long ld[1] = {0};
     if (read) patch_op(GA_GET, g_b, &lo, &hi, r.p, ld, nullptr);
@@ -1998,12 +1926,11 @@ static void pack_call(bool unpack, int g_src, int g_dst, int g_msk, long lo, lon
     comex_barrier(COMEX_GROUP_WORLD);
     (unpack ? g_stat.numunpack : g_stat.numpack)++;
     const int me = my_rank(), np = world_size();
-    const Sub sf = own_sub(full, &lo, &hi), sm = own_sub(msk, &lo, &hi);
+    const Sub sf = own_sub(full, Patch(lo, hi)), sm = own_sub(msk, Patch(lo, hi));
     std::vector<long> counts((size_t)np, 0);
     if (sm.any) {
         long long c = 0;
-        const int rc = gaamd_mask_count(msk.optype, sm.count[0], sm.p, &c, gaamd_stream());
-        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        launched(gaamd_mask_count(msk.optype, sm.count[0], sm.p, &c, gaamd_stream()), what);
         counts[(size_t)me] = (long)c;
     }
     exchange_slots(counts);
@@ -2020,9 +1947,9 @@ static void pack_call(bool unpack, int g_src, int g_dst, int g_msk, long lo, lon
     if (cnt > 0) {
         const long n = sm.count[0];
         VecPart v = packed_part(g_thin, place, cnt, n, unpack, what);
-        const int rc = unpack ? gaamd_mask_unpack(full.optype, msk.optype, n, v.p, sm.p, sf.p, gaamd_stream())
-                              : gaamd_mask_pack(full.optype, msk.optype, n, sf.p, sm.p, v.p, gaamd_stream());
-        if (rc) fatal("%s: kernel launch failed (%d)", what, rc);
+        launched(unpack ? gaamd_mask_unpack(full.optype, msk.optype, n, v.p, sm.p, sf.p, gaamd_stream())
+                        : gaamd_mask_pack(full.optype, msk.optype, n, sf.p, sm.p, v.p, gaamd_stream()),
+                 what);
         vec_done(g_thin, place + 1, place + cnt, v, unpack ? V_READ : V_WRITE, what);
         g_stat.mathloc += 3.0 * sm.bytes + 2.0 * cnt * full.elemsize;   // msk three times, cnt elements in and out
     }

@@ -172,7 +172,7 @@ static void gemm_span(const void *base, long long rows, long long len, long long
 int plan_gemm(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
               const void *a, long long lda, const void *b, long long ldb, const void *beta, const void *c,
               long long ldc, long long plan[6]) {
-    const int esz = op == 38 ? 8 : op == 39 ? 4 : 0;   // COMEX_ACC_DBL, COMEX_ACC_FLT
+    const int esz = op == COMEX_ACC_DBL ? 8 : op == COMEX_ACC_FLT ? 4 : 0;
     const int ta = gemm_trans(transa), tb = gemm_trans(transb);
     if (!esz || ta < 0 || tb < 0) return kPatchErrOp;
     if (m < 0 || n < 0 || k < 0) return kPatchErrCount;
@@ -221,7 +221,7 @@ int launch_gemm(int op, int transa, int transb, long long m, long long n, long l
     const int rc = plan_gemm(op, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, plan);
     if (rc) return rc < 0 ? rc : 0;
     bool alpha0, beta0;
-    if (op == 38) {
+    if (op == COMEX_ACC_DBL) {
         double al, be;
         memcpy(&al, alpha, 8);
         memcpy(&be, beta, 8);
@@ -236,13 +236,13 @@ int launch_gemm(int op, int transa, int transb, long long m, long long n, long l
     }
     if (alpha0 || k == 0) {
         // A and B are not read: C = beta * C, by the patch kernels (beta == 0: C = 0, not read)
-        const long long count[2] = {n, m}, stride[1] = {ldc * (op == 38 ? 8 : 4)};
+        const long long count[2] = {n, m}, stride[1] = {ldc * (op == COMEX_ACC_DBL ? 8 : 4)};
         const double zero = 0.0;
         return beta0 ? launch_patch_fill(op, &zero, c, stride, count, 2, stream)
                      : launch_patch_scale(op, beta, c, stride, count, 2, stream);
     }
     const int ta = gemm_trans(transa), tb = gemm_trans(transb);
-    const hipError_t e = op == 38 ? go_gemm<double>(ta, tb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, plan, stream)
+    const hipError_t e = op == COMEX_ACC_DBL ? go_gemm<double>(ta, tb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, plan, stream)
                                   : go_gemm<float>(ta, tb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, plan, stream);
     return e == hipSuccess ? 0 : -100 - (int)e;
 }

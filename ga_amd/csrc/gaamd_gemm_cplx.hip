@@ -216,7 +216,7 @@ static int cgemm_trans(int c) {
 int plan_gemm_cplx(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
                    const void *a, long long lda, const void *b, long long ldb, const void *beta, const void *c,
                    long long ldc, long long plan[6]) {
-    const int esz = op == 41 ? 16 : op == 40 ? 8 : 0;   // COMEX_ACC_DCP, COMEX_ACC_CPL
+    const int esz = op == COMEX_ACC_DCP ? 16 : op == COMEX_ACC_CPL ? 8 : 0;
     const int ta = cgemm_trans(transa), tb = cgemm_trans(transb);
     if (!esz || ta < 0 || tb < 0) return kPatchErrOp;
     if (m < 0 || n < 0 || k < 0) return kPatchErrCount;
@@ -231,7 +231,7 @@ int plan_gemm_cplx(int op, int transa, int transb, long long m, long long n, lon
     gemm_span(b, b_rows, b_len, ldb, esz, blo, bhi);
     gemm_span(c, m, n, ldc, esz, clo, chi);
     if ((clo < ahi && alo < chi) || (clo < bhi && blo < chi)) return kPatchErrOverlap;
-    const long long TN = op == 41 ? kCGemmTN_DCP : kCGemmTN_CPL, TK = op == 41 ? kCGemmTK_DCP : kCGemmTK_CPL;
+    const long long TN = op == COMEX_ACC_DCP ? kCGemmTN_DCP : kCGemmTN_CPL, TK = op == COMEX_ACC_DCP ? kCGemmTK_DCP : kCGemmTK_CPL;
     const long long tm = (m + kCGemmTM - 1) / kCGemmTM, tn = (n + TN - 1) / TN;
     if (tm > 0 && tn > 0x7fffffffll / tm) return kPatchErrRange;
     if (plan) {
@@ -268,7 +268,7 @@ int launch_gemm_cplx(int op, int transa, int transb, long long m, long long n, l
     double ald[2], bed[2];
     float alf[2], bef[2];
     bool alpha0, beta0;
-    if (op == 41) {
+    if (op == COMEX_ACC_DCP) {
         memcpy(ald, alpha, 16);
         memcpy(bed, beta, 16);
         alpha0 = ald[0] == 0.0 && ald[1] == 0.0;
@@ -281,14 +281,14 @@ int launch_gemm_cplx(int op, int transa, int transb, long long m, long long n, l
     }
     if (alpha0 || k == 0) {
         // A and B are not read: C = beta * C, by the patch kernels (beta == 0: C = 0, not read)
-        const long long count[2] = {n, m}, stride[1] = {ldc * (op == 41 ? 16 : 8)};
+        const long long count[2] = {n, m}, stride[1] = {ldc * (op == COMEX_ACC_DCP ? 16 : 8)};
         const double zero[2] = {0.0, 0.0};
         return beta0 ? launch_patch_fill(op, zero, c, stride, count, 2, stream)
                      : launch_patch_scale(op, beta, c, stride, count, 2, stream);
     }
     const int ta = cgemm_trans(transa), tb = cgemm_trans(transb);
     const hipError_t e =
-        op == 41 ? go_gemm_cplx<double, kCGemmTN_DCP / 32, kCGemmTK_DCP>(ta, tb, m, n, k, ald, a, lda, b, ldb, bed, c, ldc,
+        op == COMEX_ACC_DCP ? go_gemm_cplx<double, kCGemmTN_DCP / 32, kCGemmTK_DCP>(ta, tb, m, n, k, ald, a, lda, b, ldb, bed, c, ldc,
                                                                         plan, stream)
                  : go_gemm_cplx<float, kCGemmTN_CPL / 32, kCGemmTK_CPL>(ta, tb, m, n, k, alf, a, lda, b, ldb, bef, c, ldc,
                                                                        plan, stream);

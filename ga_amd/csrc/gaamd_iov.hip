@@ -1241,12 +1241,12 @@ static int iov_dispatch(int op, const void *scale, int W, const IovDesc &d, bool
     hipError_t e;
     switch (op) {
     case kOpCopy: e = iov_op(W, d, CopyOp{}, serial, sys, stream, ha); break;
-    case 37: { AccInt o; int32_t s; memcpy(&s, scale, 4); o.s = (uint32_t)s; e = iov_op(W, d, o, serial, sys, stream, ha); break; }
-    case 42: { AccLng o; int64_t s; memcpy(&s, scale, 8); o.s = (uint64_t)s; e = iov_op(W, d, o, serial, sys, stream, ha); break; }
-    case 39: { AccFlt o; memcpy(&o.s, scale, 4); e = iov_op(W, d, o, serial, sys, stream, ha); break; }
-    case 38: { AccDbl o; memcpy(&o.s, scale, 8); e = iov_op(W, d, o, serial, sys, stream, ha); break; }
-    case 40: { AccCpl o; float s[2]; memcpy(s, scale, 8); o.sr = s[0]; o.si = s[1]; e = iov_op(W, d, o, serial, sys, stream, ha); break; }
-    case 41: { AccDcp o; double s[2]; memcpy(s, scale, 16); o.sr = s[0]; o.si = s[1]; e = iov_op(W, d, o, serial, sys, stream, ha); break; }
+    case COMEX_ACC_INT: { AccInt o; int32_t s; memcpy(&s, scale, 4); o.s = (uint32_t)s; e = iov_op(W, d, o, serial, sys, stream, ha); break; }
+    case COMEX_ACC_LNG: { AccLng o; int64_t s; memcpy(&s, scale, 8); o.s = (uint64_t)s; e = iov_op(W, d, o, serial, sys, stream, ha); break; }
+    case COMEX_ACC_FLT: { AccFlt o; memcpy(&o.s, scale, 4); e = iov_op(W, d, o, serial, sys, stream, ha); break; }
+    case COMEX_ACC_DBL: { AccDbl o; memcpy(&o.s, scale, 8); e = iov_op(W, d, o, serial, sys, stream, ha); break; }
+    case COMEX_ACC_CPL: { AccCpl o; float s[2]; memcpy(s, scale, 8); o.sr = s[0]; o.si = s[1]; e = iov_op(W, d, o, serial, sys, stream, ha); break; }
+    case COMEX_ACC_DCP: { AccDcp o; double s[2]; memcpy(s, scale, 16); o.sr = s[0]; o.si = s[1]; e = iov_op(W, d, o, serial, sys, stream, ha); break; }
     default: return -4;
     }
     return e == hipSuccess ? 0 : -100 - (int)e;

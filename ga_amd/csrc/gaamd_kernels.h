@@ -13,6 +13,7 @@
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
+#include "../../include/comex.h"   // COMEX_ACC_*: the element type codes
 
 namespace gaamd {
 

@@ -64,12 +64,12 @@ unsigned long long kernel_count(int kind) { return (kind >= 0 && kind < kKinds) 
 int elem_size(int op) {
     switch (op) {
     case kOpCopy: return 1;
-    case 37: return 4;   // COMEX_ACC_INT
-    case 38: return 8;   // COMEX_ACC_DBL
-    case 39: return 4;   // COMEX_ACC_FLT
-    case 40: return 8;   // COMEX_ACC_CPL
-    case 41: return 16;  // COMEX_ACC_DCP
-    case 42: return 8;   // COMEX_ACC_LNG
+    case COMEX_ACC_INT: return 4;
+    case COMEX_ACC_DBL: return 8;
+    case COMEX_ACC_FLT: return 4;
+    case COMEX_ACC_CPL: return 8;
+    case COMEX_ACC_DCP: return 16;
+    case COMEX_ACC_LNG: return 8;
     default: return 0;
     }
 }
@@ -904,12 +904,12 @@ static hipError_t dispatch_op(const Plan &p, const Desc &d, const OP &op, uint64
 static hipError_t dispatch(int op, const void *scale, const Plan &p, const Desc &d, uint64_t blocks, hipStream_t st) {
     switch (op) {
     case kOpCopy: return dispatch_op(p, d, CopyOp{}, blocks, st);
-    case 37: { AccInt o; int32_t s; memcpy(&s, scale, 4); o.s = (uint32_t)s; return dispatch_op(p, d, o, blocks, st); }
-    case 42: { AccLng o; int64_t s; memcpy(&s, scale, 8); o.s = (uint64_t)s; return dispatch_op(p, d, o, blocks, st); }
-    case 39: { AccFlt o; memcpy(&o.s, scale, 4); return dispatch_op(p, d, o, blocks, st); }
-    case 38: { AccDbl o; memcpy(&o.s, scale, 8); return dispatch_op(p, d, o, blocks, st); }
-    case 40: { AccCpl o; float s[2]; memcpy(s, scale, 8); o.sr = s[0]; o.si = s[1]; return dispatch_op(p, d, o, blocks, st); }
-    case 41: { AccDcp o; double s[2]; memcpy(s, scale, 16); o.sr = s[0]; o.si = s[1]; return dispatch_op(p, d, o, blocks, st); }
+    case COMEX_ACC_INT: { AccInt o; int32_t s; memcpy(&s, scale, 4); o.s = (uint32_t)s; return dispatch_op(p, d, o, blocks, st); }
+    case COMEX_ACC_LNG: { AccLng o; int64_t s; memcpy(&s, scale, 8); o.s = (uint64_t)s; return dispatch_op(p, d, o, blocks, st); }
+    case COMEX_ACC_FLT: { AccFlt o; memcpy(&o.s, scale, 4); return dispatch_op(p, d, o, blocks, st); }
+    case COMEX_ACC_DBL: { AccDbl o; memcpy(&o.s, scale, 8); return dispatch_op(p, d, o, blocks, st); }
+    case COMEX_ACC_CPL: { AccCpl o; float s[2]; memcpy(s, scale, 8); o.sr = s[0]; o.si = s[1]; return dispatch_op(p, d, o, blocks, st); }
+    case COMEX_ACC_DCP: { AccDcp o; double s[2]; memcpy(s, scale, 16); o.sr = s[0]; o.si = s[1]; return dispatch_op(p, d, o, blocks, st); }
     }
     return hipErrorInvalidValue;
 }
@@ -1249,7 +1249,7 @@ int launch_strided(int op, const void *scale, const void *src, const int *src_st
     // meeting a dst row): rows split over workgroups with atomic partials -- wrapping
     // integer sums are exact in any order; device-scope atomics need the dst in HBM
     bool cols_atomic = false, cols_sum = false;
-    if (cols && ov == OV_COLS && (op == 37 || op == 42) && tn.ordered_cols == 2 &&
+    if (cols && ov == OV_COLS && (op == COMEX_ACC_INT || op == COMEX_ACC_LNG) && tn.ordered_cols == 2 &&
         ((uint64_t)(uintptr_t)dst & (esz - 1)) == 0) {
         hipPointerAttribute_t at;
         memset(&at, 0, sizeof(at));

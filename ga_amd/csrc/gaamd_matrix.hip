@@ -117,31 +117,25 @@ __global__ __launch_bounds__(kDotBS) void k_patch_norm(const PatchDesc d, const 
 }
 
 template <class OP, int W>
-static hipError_t go_norm(const PatchDesc &d, uint32_t items, FastDiv cd, uint32_t nwg, DotScratch *s, hipStream_t st) {
+static hipError_t go_norm(const PatchReduce &r, hipStream_t st) {
     typedef typename OP::acc_t A;
-    if (d.levels <= 1)
-        hipLaunchKernelGGL((k_patch_norm<OP, W, 1>), dim3(nwg), dim3(kDotBS), 0, st, d, items, cd, (A *)s->part);
+    if (r.d.levels <= 1)
+        hipLaunchKernelGGL((k_patch_norm<OP, W, 1>), dim3(r.nwg), dim3(kDotBS), 0, st, r.d, r.items, r.cd, (A *)r.s->part);
     else
-        hipLaunchKernelGGL((k_patch_norm<OP, W, 0>), dim3(nwg), dim3(kDotBS), 0, st, d, items, cd, (A *)s->part);
+        hipLaunchKernelGGL((k_patch_norm<OP, W, 0>), dim3(r.nwg), dim3(kDotBS), 0, st, r.d, r.items, r.cd, (A *)r.s->part);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_patch_dot_final<A, 1>), dim3(1), dim3(kDotBS), 0, st, (const A *)s->part, nwg, (A *)s->res_dev);
+    hipLaunchKernelGGL((k_patch_dot_final<A, 1>), dim3(1), dim3(kDotBS), 0, st, (const A *)r.s->part, r.nwg,
+                       (A *)r.s->res_dev);
     return hipGetLastError();
 }
 
 template <typename T, bool CPLX, int ELEM>
-static hipError_t go_norm_w(bool inf, int W, const PatchDesc &d, uint32_t items, FastDiv cd, uint32_t nwg, DotScratch *s,
-                            hipStream_t st) {
-    typedef PatchNorm<T, CPLX, false> One;
-    typedef PatchNorm<T, CPLX, true> Inf;
-    if (W == 16) return inf ? go_norm<Inf, 16>(d, items, cd, nwg, s, st) : go_norm<One, 16>(d, items, cd, nwg, s, st);
-    if constexpr (ELEM <= 8) {
-        if (W == 8) return inf ? go_norm<Inf, 8>(d, items, cd, nwg, s, st) : go_norm<One, 8>(d, items, cd, nwg, s, st);
-    }
-    if constexpr (ELEM <= 4) {
-        if (W == 4) return inf ? go_norm<Inf, 4>(d, items, cd, nwg, s, st) : go_norm<One, 4>(d, items, cd, nwg, s, st);
-    }
-    return hipErrorInvalidValue;
+static hipError_t go_norm_w(bool inf, int W, const PatchReduce &r, hipStream_t st) {
+    return with_width<ELEM>(W, [&](auto w) {
+        constexpr int VW = decltype(w)::value;
+        return inf ? go_norm<PatchNorm<T, CPLX, true>, VW>(r, st) : go_norm<PatchNorm<T, CPLX, false>, VW>(r, st);
+    });
 }
 
 int launch_patch_norm(int op, int kind, const void *a, const long long *a_stride, const long long *count, int ndim,
@@ -153,43 +147,31 @@ int launch_patch_norm(int op, int kind, const void *a, const long long *a_stride
     if (rc < 0) return rc;
     if (kind != kNormOne && kind != kNormInf) return kPatchErrOp;
     if (!result) return kPatchErrScalar;
-    const int rsz = op == 40 ? 4 : op == 41 ? 8 : p.esz;   // complex: the real type
+    const int rsz = op == COMEX_ACC_CPL ? 4 : op == COMEX_ACC_DCP ? 8 : p.esz;   // complex: the real type
     if (rc == 1) {   // an empty patch: the norm of nothing
         memset(result, 0, (size_t)rsz);
         return 0;
     }
-    PatchDesc d;
-    fill_desc(d, p, 1, base);
-    const uint64_t chunks = (d.nvec + kDotBS - 1) / kDotBS;
-    const uint64_t items = chunks * p.rows;
-    if (chunks >= (1ull << 31) || items >= (1ull << 31)) return kPatchErrRange;
-    const uint32_t nwg = (uint32_t)((items + kDotItems - 1) / kDotItems);
-    DotScratch *s = dot_scratch((size_t)nwg * 8);
-    if (!s) return -100 - (int)hipGetLastError();
-    const FastDiv cd = make_fastdiv((uint32_t)chunks);
+    PatchReduce r;
+    int err = patch_reduce(p, 1, base, 8, r);
+    if (err) return err;
     const bool inf = kind == kNormInf;
-    hipError_t e = hipErrorInvalidValue;
-    switch (op) {
-    case 37: e = go_norm_w<int32_t, false, 4>(inf, p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
-    case 38: e = go_norm_w<double, false, 8>(inf, p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
-    case 39: e = go_norm_w<float, false, 4>(inf, p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
-    case 40: e = go_norm_w<float, true, 8>(inf, p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
-    case 41: e = go_norm_w<double, true, 16>(inf, p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
-    case 42: e = go_norm_w<int64_t, false, 8>(inf, p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
-    }
-    if (e != hipSuccess) return rc_of(e);
-    e = stream ? hipStreamSynchronize(stream) : hipDeviceSynchronize();
-    if (e != hipSuccess) return rc_of(e);
+    const hipError_t e = for_type<int32_t, int64_t>(op, [&](auto t) {
+        typedef decltype(t) T;
+        return go_norm_w<typename T::real, T::parts == 2, T::elem>(inf, p.W, r, stream);
+    });
+    const char *res = patch_result(r.s, e, stream, err);
+    if (!res) return err;
     if (inf) {   // the key back to the value's bits
         if (rsz == 4) {
-            const uint32_t b = rd<uint32_t>(s->res_host) ^ 0x80000000u;
+            const uint32_t b = rd<uint32_t>(res) ^ 0x80000000u;
             memcpy(result, &b, 4);
         } else {
-            const uint64_t b = rd<uint64_t>(s->res_host) ^ 0x8000000000000000ull;
+            const uint64_t b = rd<uint64_t>(res) ^ 0x8000000000000000ull;
             memcpy(result, &b, 8);
         }
     } else {
-        memcpy(result, s->res_host, (size_t)rsz);
+        memcpy(result, res, (size_t)rsz);
     }
     return 0;
 }
@@ -294,16 +276,10 @@ int launch_diagonal(int op, int fn, long long n, void *a, long long a_step, void
     d.fn = fn;
     if (fn == kDiagShift) memcpy(&d.s, scalar, (size_t)esz);
     const bool whole = !(al & (uint64_t)(esz - 1));
-    hipError_t e = hipErrorInvalidValue;
-    switch (op) {
-    case 37: e = go_diagonal<uint32_t, 1>(d, true, stream); break;
-    case 38: e = go_diagonal<double, 1>(d, true, stream); break;
-    case 39: e = go_diagonal<float, 1>(d, true, stream); break;
-    case 40: e = go_diagonal<float, 2>(d, whole, stream); break;
-    case 41: e = go_diagonal<double, 2>(d, whole, stream); break;
-    case 42: e = go_diagonal<uint64_t, 1>(d, true, stream); break;
-    }
-    return rc_of(e);
+    return rc_of(for_type(op, [&](auto t) {   // a one-part element is always moved whole
+        typedef decltype(t) T;
+        return go_diagonal<typename T::real, T::parts>(d, T::parts == 1 || whole, stream);
+    }));
 }
 
 // ---------------------------------------------------------------------------
@@ -386,13 +362,11 @@ static hipError_t go_scale_rc(ScaleRcDesc d, uint64_t rows, bool cols, hipStream
 // go_map_w's shapes for an operation that loads its output
 template <typename P>
 static hipError_t go_scale_rc_w(int W, int block, const ScaleRcDesc &d, uint64_t rows, bool cols, hipStream_t st) {
-    if (W == 16)
-        return block == 64 ? go_scale_rc<P, 16, 64, 1>(d, rows, cols, st) : go_scale_rc<P, 16, 128, 1>(d, rows, cols, st);
-    if (W == 8) return go_scale_rc<P, 8, 128, 2>(d, rows, cols, st);
-    if constexpr (sizeof(P) == 4) {
-        if (W == 4) return go_scale_rc<P, 4, 128, 4>(d, rows, cols, st);
-    }
-    return hipErrorInvalidValue;
+    return with_width<(int)sizeof(P)>(W, [&](auto w) {
+        constexpr int VW = decltype(w)::value;
+        if (VW == 16 && block == 64) return go_scale_rc<P, 16, 64, 1>(d, rows, cols, st);
+        return go_scale_rc<P, VW, 128, 16 / VW>(d, rows, cols, st);
+    });
 }
 
 int launch_scale_rc(int op, bool cols, long long rows, long long ncols, void *a, long long lda, const void *v,
@@ -424,16 +398,9 @@ int launch_scale_rc(int op, bool cols, long long rows, long long ncols, void *a,
     d.nvec = row_bytes / (uint64_t)W;
     d.esz = esz;
     const int block = (W == 16 && !(al & 4095)) ? 64 : 128;
-    hipError_t e = hipErrorInvalidValue;
-    switch (op) {
-    case 37: e = go_scale_rc_w<uint32_t>(W, block, d, (uint64_t)rows, cols, stream); break;
-    case 39:
-    case 40: e = go_scale_rc_w<float>(W, block, d, (uint64_t)rows, cols, stream); break;
-    case 38:
-    case 41: e = go_scale_rc_w<double>(W, block, d, (uint64_t)rows, cols, stream); break;
-    case 42: e = go_scale_rc_w<uint64_t>(W, block, d, (uint64_t)rows, cols, stream); break;
-    }
-    return rc_of(e);
+    return rc_of(for_type(op, [&](auto t) {   // complex part by part: only the real type matters
+        return go_scale_rc_w<typename decltype(t)::real>(W, block, d, (uint64_t)rows, cols, stream);
+    }));
 }
 
 }  // namespace gaamd

@@ -794,25 +794,53 @@ static hipError_t go_map(PatchDesc d, const PatchPlan &p, const OP &op, hipStrea
     return hipSuccess;
 }
 
+// the plan's vector width W (W >= ELEM, the bytes of one element, always) as a compile-time
+// constant: f(std::integral_constant<int, W>)
+template <int ELEM, class F>
+static hipError_t with_width(int W, F &&f) {
+    if (W == 16) return f(std::integral_constant<int, 16>());
+    if constexpr (ELEM <= 8) {
+        if (W == 8) return f(std::integral_constant<int, 8>());
+    }
+    if constexpr (ELEM <= 4) {
+        if (W == 4) return f(std::integral_constant<int, 4>());
+    }
+    return hipErrorInvalidValue;
+}
+
+// the element type a COMEX_ACC_* code names: f(TypeTag<real type, parts>).  The families read
+// integers differently: I32 / I64 are unsigned for scale, add, dot, scan, enum and the
+// diagonals (wrapping arithmetic), signed for elem, norm and select (ordering, abs).
+template <typename T, int NP>
+struct TypeTag {
+    typedef T real;
+    static constexpr int parts = NP, elem = NP * (int)sizeof(T);
+};
+template <typename I32 = uint32_t, typename I64 = uint64_t, class F>
+static hipError_t for_type(int op, F &&f) {
+    switch (op) {
+    case COMEX_ACC_INT: return f(TypeTag<I32, 1>());
+    case COMEX_ACC_DBL: return f(TypeTag<double, 1>());
+    case COMEX_ACC_FLT: return f(TypeTag<float, 1>());
+    case COMEX_ACC_CPL: return f(TypeTag<float, 2>());
+    case COMEX_ACC_DCP: return f(TypeTag<double, 2>());
+    case COMEX_ACC_LNG: return f(TypeTag<I64, 1>());
+    }
+    return hipErrorInvalidValue;
+}
+
 // ELEM: bytes of one element (W >= ELEM always).  A store-only operation (fill) has no
 // loads to keep in flight: 256-thread blocks of 4 vectors per lane (16 KiB at W = 16).
 template <class OP, int ELEM>
 static hipError_t go_map_w(const PatchDesc &d, const PatchPlan &p, const OP &op, hipStream_t st) {
     if constexpr (OP::kIn == 0) {
-        if (p.W == 16) return go_map<OP, 16, 256, 4>(d, p, op, st);
-        if (p.W == 8) return go_map<OP, 8, 256, 4>(d, p, op, st);
-        if (p.W == 4) return go_map<OP, 4, 256, 4>(d, p, op, st);
-        return hipErrorInvalidValue;
-    } else {
-        if (p.W == 16)
-            return p.block == 64 ? go_map<OP, 16, 64, 1>(d, p, op, st) : go_map<OP, 16, 128, 1>(d, p, op, st);
-        if constexpr (ELEM <= 8) {
-            if (p.W == 8) return go_map<OP, 8, 128, 2>(d, p, op, st);
-        }
-        if constexpr (ELEM <= 4) {
-            if (p.W == 4) return go_map<OP, 4, 128, 4>(d, p, op, st);
-        }
-        return hipErrorInvalidValue;
+        return with_width<4>(p.W, [&](auto w) { return go_map<OP, decltype(w)::value, 256, 4>(d, p, op, st); });
+    } else {   // 16 bytes per lane: 128 threads of 16 / W vectors, or the plan's one-wave blocks at W = 16
+        return with_width<ELEM>(p.W, [&](auto w) {
+            constexpr int W = decltype(w)::value;
+            if (W == 16 && p.block == 64) return go_map<OP, 16, 64, 1>(d, p, op, st);
+            return go_map<OP, W, 128, 16 / W>(d, p, op, st);
+        });
     }
 }
 
@@ -849,21 +877,14 @@ int launch_patch_scale(int op, const void *alpha, void *dst, const long long *ds
     if (!alpha) return kPatchErrScalar;
     PatchDesc d;
     fill_desc(d, p, 1, base);
-    hipError_t e = hipErrorInvalidValue;
-    switch (op) {
-    case 37: e = go_map_w<PatchScaleReal<uint32_t>, 4>(d, p, PatchScaleReal<uint32_t>{rd<uint32_t>(alpha)}, stream); break;
-    case 38: e = go_map_w<PatchScaleReal<double>, 8>(d, p, PatchScaleReal<double>{rd<double>(alpha)}, stream); break;
-    case 39: e = go_map_w<PatchScaleReal<float>, 4>(d, p, PatchScaleReal<float>{rd<float>(alpha)}, stream); break;
-    case 40:
-        e = go_map_w<PatchScaleCplx<float>, 8>(d, p, PatchScaleCplx<float>{rd<float>(alpha), rd<float>(alpha, 1)}, stream);
-        break;
-    case 41:
-        e = go_map_w<PatchScaleCplx<double>, 16>(d, p, PatchScaleCplx<double>{rd<double>(alpha), rd<double>(alpha, 1)},
-                                                 stream);
-        break;
-    case 42: e = go_map_w<PatchScaleReal<uint64_t>, 8>(d, p, PatchScaleReal<uint64_t>{rd<uint64_t>(alpha)}, stream); break;
-    }
-    return rc_of(e);
+    return rc_of(for_type(op, [&](auto t) {
+        typedef typename decltype(t)::real T;
+        constexpr int E = decltype(t)::elem;
+        if constexpr (decltype(t)::parts == 1)
+            return go_map_w<PatchScaleReal<T>, E>(d, p, PatchScaleReal<T>{rd<T>(alpha)}, stream);
+        else
+            return go_map_w<PatchScaleCplx<T>, E>(d, p, PatchScaleCplx<T>{rd<T>(alpha), rd<T>(alpha, 1)}, stream);
+    }));
 }
 
 // the checks of launch_patch_add without a launch (no device needed); plan[0..3] =
@@ -898,33 +919,15 @@ int launch_patch_add(int op, const void *alpha, const void *a, const long long *
     const void *base[3] = {c, a, b};
     PatchDesc d;
     fill_desc(d, p, 3, base);
-    hipError_t e = hipErrorInvalidValue;
-    switch (op) {
-    case 37:
-        e = go_map_w<PatchAddReal<uint32_t>, 4>(d, p, PatchAddReal<uint32_t>{rd<uint32_t>(alpha), rd<uint32_t>(beta)},
-                                                stream);
-        break;
-    case 38:
-        e = go_map_w<PatchAddReal<double>, 8>(d, p, PatchAddReal<double>{rd<double>(alpha), rd<double>(beta)}, stream);
-        break;
-    case 39:
-        e = go_map_w<PatchAddReal<float>, 4>(d, p, PatchAddReal<float>{rd<float>(alpha), rd<float>(beta)}, stream);
-        break;
-    case 40:
-        e = go_map_w<PatchAddCplx<float>, 8>(
-            d, p, PatchAddCplx<float>{rd<float>(alpha), rd<float>(alpha, 1), rd<float>(beta), rd<float>(beta, 1)}, stream);
-        break;
-    case 41:
-        e = go_map_w<PatchAddCplx<double>, 16>(
-            d, p, PatchAddCplx<double>{rd<double>(alpha), rd<double>(alpha, 1), rd<double>(beta), rd<double>(beta, 1)},
-            stream);
-        break;
-    case 42:
-        e = go_map_w<PatchAddReal<uint64_t>, 8>(d, p, PatchAddReal<uint64_t>{rd<uint64_t>(alpha), rd<uint64_t>(beta)},
-                                                stream);
-        break;
-    }
-    return rc_of(e);
+    return rc_of(for_type(op, [&](auto t) {
+        typedef typename decltype(t)::real T;
+        constexpr int E = decltype(t)::elem;
+        if constexpr (decltype(t)::parts == 1)
+            return go_map_w<PatchAddReal<T>, E>(d, p, PatchAddReal<T>{rd<T>(alpha), rd<T>(beta)}, stream);
+        else
+            return go_map_w<PatchAddCplx<T>, E>(
+                d, p, PatchAddCplx<T>{rd<T>(alpha), rd<T>(alpha, 1), rd<T>(beta), rd<T>(beta, 1)}, stream);
+    }));
 }
 
 // ---------------------------------------------------------------------------
@@ -983,32 +986,50 @@ static DotScratch *dot_scratch(size_t bytes) {
     return &s;
 }
 
-template <class OP, int W>
-static hipError_t go_dot(const PatchDesc &d, uint32_t items, FastDiv chunk_div, uint32_t nwg, DotScratch *s,
-                         hipStream_t st) {
-    typedef typename OP::acc_t A;
-    if (d.levels <= 1)
-        hipLaunchKernelGGL((k_patch_dot<OP, W, 1>), dim3(nwg), dim3(kDotBS), 0, st, d, items, chunk_div, (A *)s->part);
-    else
-        hipLaunchKernelGGL((k_patch_dot<OP, W, 0>), dim3(nwg), dim3(kDotBS), 0, st, d, items, chunk_div, (A *)s->part);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_patch_dot_final<A, OP::kAcc>), dim3(1), dim3(kDotBS), 0, st, (const A *)s->part, nwg,
-                       (A *)s->res_dev);
-    return hipGetLastError();
+// The launch of a reduction over a patch (dot; norm in gaamd_matrix.hip, select in
+// gaamd_select.hip): the rows in chunks of kDotBS vectors, kDotItems (row, chunk) items per
+// workgroup, one partial of `part_bytes` per workgroup in the thread's scratch.
+struct PatchReduce {
+    PatchDesc d;
+    uint32_t items = 0, nwg = 0;
+    FastDiv cd;
+    DotScratch *s = nullptr;
+};
+
+// 0, or the launcher's error code
+static int patch_reduce(const PatchPlan &p, int nops, const void *const *base, size_t part_bytes, PatchReduce &r) {
+    fill_desc(r.d, p, nops, base);
+    const uint64_t chunks = (r.d.nvec + kDotBS - 1) / kDotBS;
+    const uint64_t items = chunks * p.rows;
+    if (chunks >= (1ull << 31) || items >= (1ull << 31)) return kPatchErrRange;
+    r.items = (uint32_t)items;
+    r.nwg = (uint32_t)((items + kDotItems - 1) / kDotItems);
+    r.s = dot_scratch((size_t)r.nwg * part_bytes);
+    if (!r.s) return -100 - (int)hipGetLastError();
+    r.cd = make_fastdiv((uint32_t)chunks);
+    return 0;
 }
 
-template <class OP, int ELEM>
-static hipError_t go_dot_w(int W, const PatchDesc &d, uint32_t items, FastDiv cd, uint32_t nwg, DotScratch *s,
-                           hipStream_t st) {
-    if (W == 16) return go_dot<OP, 16>(d, items, cd, nwg, s, st);
-    if constexpr (ELEM <= 8) {
-        if (W == 8) return go_dot<OP, 8>(d, items, cd, nwg, s, st);
-    }
-    if constexpr (ELEM <= 4) {
-        if (W == 4) return go_dot<OP, 4>(d, items, cd, nwg, s, st);
-    }
-    return hipErrorInvalidValue;
+// after the launches (`e`: their error): waits for the stream; the pinned result block, or
+// null with the error code in rc
+static const char *patch_result(const DotScratch *s, hipError_t e, hipStream_t stream, int &rc) {
+    if (e == hipSuccess) e = stream ? hipStreamSynchronize(stream) : hipDeviceSynchronize();
+    rc = rc_of(e);
+    return rc ? nullptr : (const char *)s->res_host;
+}
+
+template <class OP, int W>
+static hipError_t go_dot(const PatchReduce &r, hipStream_t st) {
+    typedef typename OP::acc_t A;
+    if (r.d.levels <= 1)
+        hipLaunchKernelGGL((k_patch_dot<OP, W, 1>), dim3(r.nwg), dim3(kDotBS), 0, st, r.d, r.items, r.cd, (A *)r.s->part);
+    else
+        hipLaunchKernelGGL((k_patch_dot<OP, W, 0>), dim3(r.nwg), dim3(kDotBS), 0, st, r.d, r.items, r.cd, (A *)r.s->part);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_patch_dot_final<A, OP::kAcc>), dim3(1), dim3(kDotBS), 0, st, (const A *)r.s->part, r.nwg,
+                       (A *)r.s->res_dev);
+    return hipGetLastError();
 }
 
 int launch_patch_dot(int op, const void *a, const long long *a_stride, const void *b, const long long *b_stride,
@@ -1023,29 +1044,17 @@ int launch_patch_dot(int op, const void *a, const long long *a_stride, const voi
         memset(result, 0, (size_t)p.esz);
         return 0;
     }
-    PatchDesc d;
-    fill_desc(d, p, 2, base);
-    const uint64_t chunks = (d.nvec + kDotBS - 1) / kDotBS;
-    const uint64_t items = chunks * p.rows;
-    if (chunks >= (1ull << 31) || items >= (1ull << 31)) return kPatchErrRange;
-    const uint32_t nwg = (uint32_t)((items + kDotItems - 1) / kDotItems);
-    DotScratch *s = dot_scratch((size_t)nwg * 16);
-    if (!s) return -100 - (int)hipGetLastError();
-    const FastDiv cd = make_fastdiv((uint32_t)chunks);
-    hipError_t e = hipErrorInvalidValue;
-    switch (op) {
-    case 37: e = go_dot_w<PatchDotReal<uint32_t>, 4>(p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
-    case 38: e = go_dot_w<PatchDotReal<double>, 8>(p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
-    case 39: e = go_dot_w<PatchDotReal<float>, 4>(p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
-    case 40: e = go_dot_w<PatchDotCplx<float>, 8>(p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
-    case 41: e = go_dot_w<PatchDotCplx<double>, 16>(p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
-    case 42: e = go_dot_w<PatchDotReal<uint64_t>, 8>(p.W, d, (uint32_t)items, cd, nwg, s, stream); break;
-    }
-    if (e != hipSuccess) return rc_of(e);
-    e = stream ? hipStreamSynchronize(stream) : hipDeviceSynchronize();
-    if (e != hipSuccess) return rc_of(e);
-    memcpy(result, s->res_host, (size_t)p.esz);
-    return 0;
+    PatchReduce r;
+    int err = patch_reduce(p, 2, base, 16, r);
+    if (err) return err;
+    const hipError_t e = for_type(op, [&](auto t) {
+        typedef typename decltype(t)::real T;
+        typedef std::conditional_t<decltype(t)::parts == 1, PatchDotReal<T>, PatchDotCplx<T>> OP;
+        return with_width<decltype(t)::elem>(p.W, [&](auto w) { return go_dot<OP, decltype(w)::value>(r, stream); });
+    });
+    const char *res = patch_result(r.s, e, stream, err);
+    if (res) memcpy(result, res, (size_t)p.esz);
+    return err;
 }
 
 // ---------------------------------------------------------------------------
@@ -1055,23 +1064,14 @@ static hipError_t go_elem(int op, const PatchDesc &d, const PatchPlan &p, const 
                           hipStream_t st) {
     const double zero[2] = {0.0, 0.0};
     if (!s) s = zero;
-    switch (op) {
-    case 37:
-        return go_map_w<PatchElemReal<F, int32_t, KIN>, 4>(d, p, PatchElemReal<F, int32_t, KIN>{rd<int32_t>(s), flag}, st);
-    case 38:
-        return go_map_w<PatchElemReal<F, double, KIN>, 8>(d, p, PatchElemReal<F, double, KIN>{rd<double>(s), flag}, st);
-    case 39:
-        return go_map_w<PatchElemReal<F, float, KIN>, 4>(d, p, PatchElemReal<F, float, KIN>{rd<float>(s), flag}, st);
-    case 40:
-        return go_map_w<PatchElemCplx<F, float, KIN>, 8>(
-            d, p, PatchElemCplx<F, float, KIN>{rd<float>(s), rd<float>(s, 1), flag}, st);
-    case 41:
-        return go_map_w<PatchElemCplx<F, double, KIN>, 16>(
-            d, p, PatchElemCplx<F, double, KIN>{rd<double>(s), rd<double>(s, 1), flag}, st);
-    case 42:
-        return go_map_w<PatchElemReal<F, int64_t, KIN>, 8>(d, p, PatchElemReal<F, int64_t, KIN>{rd<int64_t>(s), flag}, st);
-    }
-    return hipErrorInvalidValue;
+    return for_type<int32_t, int64_t>(op, [&](auto t) {
+        typedef typename decltype(t)::real T;
+        constexpr int E = decltype(t)::elem;
+        if constexpr (decltype(t)::parts == 1)
+            return go_map_w<PatchElemReal<F, T, KIN>, E>(d, p, PatchElemReal<F, T, KIN>{rd<T>(s), flag}, st);
+        else
+            return go_map_w<PatchElemCplx<F, T, KIN>, E>(d, p, PatchElemCplx<F, T, KIN>{rd<T>(s), rd<T>(s, 1), flag}, st);
+    });
 }
 
 // RECIP and DIV: the flag word cleared before the launch, read after the stream has finished
@@ -1081,10 +1081,9 @@ static int go_elem_checked(int op, const PatchDesc &d, const PatchPlan &p, hipSt
     if (!s) return -100 - (int)hipGetLastError();
     volatile uint32_t *flag = (volatile uint32_t *)((char *)s->res_host + kResFlag);
     *flag = 0;
-    hipError_t e = go_elem<F, KIN>(op, d, p, nullptr, (uint32_t *)((char *)s->res_dev + kResFlag), stream);
-    if (e != hipSuccess) return rc_of(e);
-    e = stream ? hipStreamSynchronize(stream) : hipDeviceSynchronize();
-    if (e != hipSuccess) return rc_of(e);
+    const hipError_t e = go_elem<F, KIN>(op, d, p, nullptr, (uint32_t *)((char *)s->res_dev + kResFlag), stream);
+    int rc;
+    if (!patch_result(s, e, stream, rc)) return rc;
     return *flag ? kPatchZeroDivisor : 0;
 }
 

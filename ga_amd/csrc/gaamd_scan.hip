@@ -497,15 +497,15 @@ __global__ __launch_bounds__(kScanBS) void k_enum(char *dst, const uint64_t n, c
 // host side
 static int scan_width(const void *p) { return (int)lowbit((uint64_t)(uintptr_t)p | 16); }
 
-static bool scan_type_ok(int op) { return op >= 37 && op <= 42; }
+static bool scan_type_ok(int op) { return op >= COMEX_ACC_INT && op <= COMEX_ACC_LNG; }
 
 // which 4-byte words of a mask element hold a sign bit
 static uint32_t mask_sign_words(int mop) {
     switch (mop) {
-    case 39: return 1u;    // float
-    case 38: return 2u;    // double: the high word
-    case 40: return 3u;    // float complex
-    case 41: return 10u;   // double complex: words 1 and 3
+    case COMEX_ACC_FLT: return 1u;    // float
+    case COMEX_ACC_DBL: return 2u;    // double: the high word
+    case COMEX_ACC_CPL: return 3u;    // float complex
+    case COMEX_ACC_DCP: return 10u;   // double complex: words 1 and 3
     }
     return 0u;
 }
@@ -575,15 +575,10 @@ static hipError_t go_scan_op(int op, int fn, bool tail, const ScanDesc &d, uint3
         }
         return hipErrorInvalidValue;
     }
-    switch (op) {
-    case 37: return go_scan<uint32_t, 1, true>(tail, d, ntiles, sc, open, carry, st);
-    case 38: return go_scan<double, 1, true>(tail, d, ntiles, sc, open, carry, st);
-    case 39: return go_scan<float, 1, true>(tail, d, ntiles, sc, open, carry, st);
-    case 40: return go_scan<float, 2, true>(tail, d, ntiles, sc, open, carry, st);
-    case 41: return go_scan<double, 2, true>(tail, d, ntiles, sc, open, carry, st);
-    case 42: return go_scan<uint64_t, 1, true>(tail, d, ntiles, sc, open, carry, st);
-    }
-    return hipErrorInvalidValue;
+    return for_type(op, [&](auto t) {
+        typedef decltype(t) T;
+        return go_scan<typename T::real, T::parts, true>(tail, d, ntiles, sc, open, carry, st);
+    });
 }
 
 static bool scan_fn_ok(int fn) { return fn == kScanCopy || fn == kScanAdd || fn == kScanAddExcl; }
@@ -607,12 +602,11 @@ int launch_scan_tail(int op, int fn, int mop, long long n, const void *src, cons
     if (!scan_scratch(ntiles, sc)) return -100 - (int)hipGetLastError();
     ScanDesc d;
     scan_desc(d, mop, n, src, msk, nullptr, fn);
-    hipError_t e = go_scan_op(op, fn, true, d, ntiles, sc, 0, nullptr, stream);
-    if (e != hipSuccess) return rc_of(e);
-    e = stream ? hipStreamSynchronize(stream) : hipDeviceSynchronize();
-    if (e != hipSuccess) return rc_of(e);
-    *has_flag = rd<uint32_t>((const char *)sc.s->res_host + kResFlag) ? 1 : 0;
-    memcpy(tail, sc.s->res_host, (size_t)esz);
+    int rc;
+    const char *res = patch_result(sc.s, go_scan_op(op, fn, true, d, ntiles, sc, 0, nullptr, stream), stream, rc);
+    if (!res) return rc;
+    *has_flag = rd<uint32_t>(res + kResFlag) ? 1 : 0;
+    memcpy(tail, res, (size_t)esz);
     return 0;
 }
 
@@ -661,12 +655,10 @@ int launch_mask_count(int mop, long long n, const void *msk, long long *count, h
     if (!scan_scratch(ntiles, sc)) return -100 - (int)hipGetLastError();
     ScanDesc d;
     scan_desc(d, mop, n, nullptr, msk, nullptr, 0);
-    hipError_t e = go_mask_offsets(d, ntiles, sc, true, stream);
-    if (e != hipSuccess) return rc_of(e);
-    e = stream ? hipStreamSynchronize(stream) : hipDeviceSynchronize();
-    if (e != hipSuccess) return rc_of(e);
-    *count = (long long)rd<uint64_t>(sc.s->res_host);
-    return 0;
+    int rc;
+    const char *res = patch_result(sc.s, go_mask_offsets(d, ntiles, sc, true, stream), stream, rc);
+    if (res) *count = (long long)rd<uint64_t>(res);
+    return rc;
 }
 
 // unpack == false: `other` is packed (written), `arr` is src; true: `other` is packed (read), `arr` is dst
@@ -732,16 +724,10 @@ int launch_enum(int op, long long n, long long first, const void *start, const v
     if (n > kScanMaxN) return kPatchErrRange;
     if ((uintptr_t)dst & 3) return kPatchErrAlign;
     if (n == 0) return 0;
-    hipError_t e = hipErrorInvalidValue;
-    switch (op) {
-    case 37: e = go_enum<uint32_t, 1>(n, first, start, stride, dst, stream); break;
-    case 38: e = go_enum<double, 1>(n, first, start, stride, dst, stream); break;
-    case 39: e = go_enum<float, 1>(n, first, start, stride, dst, stream); break;
-    case 40: e = go_enum<float, 2>(n, first, start, stride, dst, stream); break;
-    case 41: e = go_enum<double, 2>(n, first, start, stride, dst, stream); break;
-    case 42: e = go_enum<uint64_t, 1>(n, first, start, stride, dst, stream); break;
-    }
-    return rc_of(e);
+    return rc_of(for_type(op, [&](auto t) {
+        typedef decltype(t) T;
+        return go_enum<typename T::real, T::parts>(n, first, start, stride, dst, stream);
+    }));
 }
 
 }  // namespace gaamd

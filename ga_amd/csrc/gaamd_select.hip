@@ -174,42 +174,32 @@ __global__ __launch_bounds__(kDotBS) void k_patch_select_final(const PatchDesc d
 }
 
 template <class OP, bool MAX, int W>
-static hipError_t go_select(const PatchDesc &d, uint32_t items, FastDiv cd, uint32_t nwg, int64_t row_elems,
-                            DotScratch *s, hipStream_t st) {
-    SelPart *part = (SelPart *)s->part;
-    if (d.levels <= 1) {
-        hipLaunchKernelGGL((k_patch_select<OP, MAX, W, 1>), dim3(nwg), dim3(kDotBS), 0, st, d, items, cd, row_elems, part);
+static hipError_t go_select(const PatchReduce &r, int64_t row_elems, hipStream_t st) {
+    SelPart *part = (SelPart *)r.s->part;
+    if (r.d.levels <= 1) {
+        hipLaunchKernelGGL((k_patch_select<OP, MAX, W, 1>), dim3(r.nwg), dim3(kDotBS), 0, st, r.d, r.items, r.cd, row_elems,
+                           part);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_patch_select_final<OP, MAX, 1>), dim3(1), dim3(kDotBS), 0, st, d, (const SelPart *)part,
-                           nwg, row_elems, (char *)s->res_dev);
+        hipLaunchKernelGGL((k_patch_select_final<OP, MAX, 1>), dim3(1), dim3(kDotBS), 0, st, r.d, (const SelPart *)part,
+                           r.nwg, row_elems, (char *)r.s->res_dev);
     } else {
-        hipLaunchKernelGGL((k_patch_select<OP, MAX, W, 0>), dim3(nwg), dim3(kDotBS), 0, st, d, items, cd, row_elems, part);
+        hipLaunchKernelGGL((k_patch_select<OP, MAX, W, 0>), dim3(r.nwg), dim3(kDotBS), 0, st, r.d, r.items, r.cd, row_elems,
+                           part);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_patch_select_final<OP, MAX, 0>), dim3(1), dim3(kDotBS), 0, st, d, (const SelPart *)part,
-                           nwg, row_elems, (char *)s->res_dev);
+        hipLaunchKernelGGL((k_patch_select_final<OP, MAX, 0>), dim3(1), dim3(kDotBS), 0, st, r.d, (const SelPart *)part,
+                           r.nwg, row_elems, (char *)r.s->res_dev);
     }
     return hipGetLastError();
 }
 
 template <class OP, int ELEM>
-static hipError_t go_select_w(bool want_max, int W, const PatchDesc &d, uint32_t items, FastDiv cd, uint32_t nwg,
-                              int64_t row_elems, DotScratch *s, hipStream_t st) {
-    if (W == 16)
-        return want_max ? go_select<OP, true, 16>(d, items, cd, nwg, row_elems, s, st)
-                        : go_select<OP, false, 16>(d, items, cd, nwg, row_elems, s, st);
-    if constexpr (ELEM <= 8) {
-        if (W == 8)
-            return want_max ? go_select<OP, true, 8>(d, items, cd, nwg, row_elems, s, st)
-                            : go_select<OP, false, 8>(d, items, cd, nwg, row_elems, s, st);
-    }
-    if constexpr (ELEM <= 4) {
-        if (W == 4)
-            return want_max ? go_select<OP, true, 4>(d, items, cd, nwg, row_elems, s, st)
-                            : go_select<OP, false, 4>(d, items, cd, nwg, row_elems, s, st);
-    }
-    return hipErrorInvalidValue;
+static hipError_t go_select_w(bool want_max, int W, const PatchReduce &r, int64_t row_elems, hipStream_t st) {
+    return with_width<ELEM>(W, [&](auto w) {
+        constexpr int VW = decltype(w)::value;
+        return want_max ? go_select<OP, true, VW>(r, row_elems, st) : go_select<OP, false, VW>(r, row_elems, st);
+    });
 }
 
 int launch_patch_select(int op, int want_max, const void *a, const long long *a_stride, const long long *count,
@@ -224,39 +214,23 @@ int launch_patch_select(int op, int want_max, const void *a, const long long *a_
         *index = -1;
         return 1;
     }
-    PatchDesc d;
-    fill_desc(d, p, 1, base);
-    const uint64_t chunks = (d.nvec + kDotBS - 1) / kDotBS;
-    const uint64_t items = chunks * p.rows;
-    if (chunks >= (1ull << 31) || items >= (1ull << 31)) return kPatchErrRange;
-    const uint32_t nwg = (uint32_t)((items + kDotItems - 1) / kDotItems);
-    DotScratch *s = dot_scratch((size_t)nwg * sizeof(SelPart));
-    if (!s) return -100 - (int)hipGetLastError();
-    const FastDiv cd = make_fastdiv((uint32_t)chunks);
+    PatchReduce r;
+    int err = patch_reduce(p, 1, base, sizeof(SelPart), r);
+    if (err) return err;
     const int64_t row_elems = (int64_t)(p.row_bytes / (uint64_t)p.esz);
     const bool mx = want_max != 0;
-    hipError_t e = hipErrorInvalidValue;
-    int ksz = p.esz;
-    switch (op) {
-    case 37: e = go_select_w<SelReal<int32_t>, 4>(mx, p.W, d, (uint32_t)items, cd, nwg, row_elems, s, stream); break;
-    case 38: e = go_select_w<SelReal<double>, 8>(mx, p.W, d, (uint32_t)items, cd, nwg, row_elems, s, stream); break;
-    case 39: e = go_select_w<SelReal<float>, 4>(mx, p.W, d, (uint32_t)items, cd, nwg, row_elems, s, stream); break;
-    case 40:
-        e = go_select_w<SelCplx<float>, 8>(mx, p.W, d, (uint32_t)items, cd, nwg, row_elems, s, stream);
-        ksz = 4;
-        break;
-    case 41:
-        e = go_select_w<SelCplx<double>, 16>(mx, p.W, d, (uint32_t)items, cd, nwg, row_elems, s, stream);
-        ksz = 8;
-        break;
-    case 42: e = go_select_w<SelReal<int64_t>, 8>(mx, p.W, d, (uint32_t)items, cd, nwg, row_elems, s, stream); break;
-    }
-    if (e != hipSuccess) return rc_of(e);
-    e = stream ? hipStreamSynchronize(stream) : hipDeviceSynchronize();
-    if (e != hipSuccess) return rc_of(e);
-    memcpy(value, s->res_host, (size_t)p.esz);
-    if (key) memcpy(key, (const char *)s->res_host + kResKey, (size_t)ksz);
-    memcpy(index, (const char *)s->res_host + kResIndex, 8);
+    int ksz = 0;   // the key: the element itself, for complex a value of its real type
+    const hipError_t e = for_type<int32_t, int64_t>(op, [&](auto t) {
+        typedef typename decltype(t)::real T;
+        typedef std::conditional_t<decltype(t)::parts == 1, SelReal<T>, SelCplx<T>> OP;
+        ksz = (int)sizeof(T);
+        return go_select_w<OP, decltype(t)::elem>(mx, p.W, r, row_elems, stream);
+    });
+    const char *res = patch_result(r.s, e, stream, err);
+    if (!res) return err;
+    memcpy(value, res, (size_t)p.esz);
+    if (key) memcpy(key, res + kResKey, (size_t)ksz);
+    memcpy(index, res + kResIndex, 8);
     return 0;
 }
 

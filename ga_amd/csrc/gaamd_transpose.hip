@@ -129,9 +129,9 @@ __global__ __launch_bounds__(256) void k_transpose(const E *__restrict__ src, E 
 // bytes per element of a COMEX_ACC_* code, 0 for anything else
 static int transpose_esz(int op) {
     switch (op) {
-    case 37: case 39: return 4;            // INT, FLT
-    case 38: case 40: case 42: return 8;   // DBL, CPL, LNG
-    case 41: return 16;                    // DCP
+    case COMEX_ACC_INT: case COMEX_ACC_FLT: return 4;
+    case COMEX_ACC_DBL: case COMEX_ACC_CPL: case COMEX_ACC_LNG: return 8;
+    case COMEX_ACC_DCP: return 16;
     }
     return 0;
 }
@@ -205,7 +205,7 @@ int launch_transpose_acc(int op, long long m, long long n, const void *alpha, co
                          long long ldc, hipStream_t stream) {
     // c is m x n and the destination, b is n x m and the source: rows = n, cols = m
     long long plan[4];
-    const int esz = op == 38 ? 8 : op == 39 ? 4 : 0;   // COMEX_ACC_DBL, COMEX_ACC_FLT
+    const int esz = op == COMEX_ACC_DBL ? 8 : op == COMEX_ACC_FLT ? 4 : 0;
     const int rc = transpose_check(esz, n, m, !alpha, b, ldb, c, ldc, plan);
     if (rc) return rc < 0 ? rc : 0;
     if (esz == 8) return go_transpose<double, kTransposeTile, true>(n, m, alpha, b, ldb, c, ldc, plan, stream);
