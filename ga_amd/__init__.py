@@ -311,6 +311,44 @@ def mask_unpack(op, mop, n, packed, msk, dst, stream=None):
     return lib().gaamd_mask_unpack(op, mop, n, _vp(packed), _vp(msk), _vp(dst), stream)
 
 
+# GA's sparse arrays at kernel level (gaamd_spmv / _sprs_diag / _sprs_scale_left / _right): a block
+# CSR in HBM -- nblk tables of nrows + 1 int offsets (block b's at offs + b * (nrows + 1)) relative to
+# start[b] (long long, in HBM too) in jdx (global columns) / val.  Addresses are ints, 0 or None is
+# NULL; the return code is handed back.
+def spmv_team(nnz_total, rows):
+    """the team (lanes per row) the GA layer uses for a matrix of nnz_total entries and `rows` rows"""
+    return lib().gaamd_spmv_team(nnz_total, rows)
+
+
+def spmv(op, nrows, nblk, offs, start, jdx, val, x, x_first, y, team, stream=None):
+    """y[r] = sum of val * x[jdx - x_first] over row r's entries, in the order contract of ga_amd.h"""
+    return lib().gaamd_spmv(op, nrows, nblk, _vp(offs), _vp(start), _vp(jdx), _vp(val), _vp(x), x_first, _vp(y), team,
+                            stream)
+
+
+def sprs_diag(op, fn, nrows, offs, jdx, val, diag_first, out, team, shift=None, stream=None):
+    """one column block: GAAMD_DIAG_GET out[r] = the last stored (r, r); GAAMD_DIAG_SHIFT every one += shift"""
+    keep, sp = scale_buffer(op, shift) if shift is not None else (None, None)
+    return lib().gaamd_sprs_diag(op, fn, nrows, _vp(offs), _vp(jdx), _vp(val), diag_first, _vp(out), sp, team, stream)
+
+
+def sprs_scale_left(op, nrows, offs, val, d, team, stream=None):
+    """one column block: val[k] = d[r] * val[k] for the entries of row r (the true complex product)"""
+    return lib().gaamd_sprs_scale_left(op, nrows, _vp(offs), _vp(val), _vp(d), team, stream)
+
+
+def sprs_scale_right(op, n, jdx, val, d, d_first, stream=None):
+    """val[k] = d[jdx[k] - d_first] * val[k], k < n (the true complex product)"""
+    return lib().gaamd_sprs_scale_right(op, n, _vp(jdx), _vp(val), _vp(d), d_first, stream)
+
+
+def sprs_range(dim, nproc, iproc):
+    """(lo, hi) of the indices of a dimension of `dim` that rank iproc of nproc owns (host only)"""
+    lo, hi = ctypes.c_long(0), ctypes.c_long(0)
+    lib().gaamd_ga_sprs_range(dim, nproc, iproc, ctypes.byref(lo), ctypes.byref(hi))
+    return lo.value, hi.value
+
+
 def patch_add_plan(op, a, a_stride, b, b_stride, c, c_stride, count):
     """gaamd_patch_add's checks without a launch (no GPU): (code, {width, levels, rows, nvec})"""
     out = (ctypes.c_longlong * 4)()

@@ -30,6 +30,7 @@
 #include "../../include/comex.h"
 #include "../../include/ga_amd.h"
 #pragma GCC visibility pop
+#include "sprs_build.hpp"
 #include <limits.h>
 #include <math.h>
 #include <stdarg.h>
@@ -93,6 +94,7 @@ static struct {
     long numselect = 0;
     long numdiag = 0, numscalerows = 0, numscalecols = 0, numnorm1 = 0, numnorminf = 0;
     long numenum = 0, numscancopy = 0, numscanadd = 0, numpack = 0, numunpack = 0;
+    long numsprs[7] = {0};   // by SprsCall
     double mathloc = 0;
 } g_stat;
 
@@ -682,7 +684,10 @@ static void destroy(int g_a) {
     a.ptr.clear();
 }
 
+static void sprs_release_all();   // the HBM of sparse arrays still alive (below)
+
 void GA_Terminate(void) {
+    sprs_release_all();
     for (size_t i = 0; i < g_arrays.size(); ++i)
         if (g_arrays[i].live) destroy((int)i + 1);
     ARMCI_Finalize();
@@ -1971,6 +1976,393 @@ void GA_Unpack(int g_src, int g_dst, int g_msk, int lo, int hi, int *icount) {
     pack_call(true, g_src, g_dst, g_msk, (long)lo + 1, (long)hi + 1, icount);
 }
 
+// ---- sparse arrays (global/src/sparse.array.c; ga.h states the contract) -------------------
+// A handle names a matrix whose rows are dealt to the ranks by gaamd_sprs::owner.  Until
+// NGA_Sprs_array_assemble the elements a rank added wait on its host; assemble moves every
+// element to the owner of its row (a table of counts through exchange_slots, then one comex_put
+// per owner into a segment of the incoming size), and the owner sorts on the host
+// (sprs_build.hpp) and uploads the block CSR into plain HBM allocations once.  The computing
+// calls run the kernels of ga_amd.h on that CSR where it lies; the vectors come through
+// vec_part / vec_done as in the matrix.c calls.
+enum SprsCall { SP_ASSEMBLE, SP_MATVEC, SP_GET_DIAG, SP_SHIFT_DIAG, SP_SCALE, SP_DIAG_LEFT, SP_DIAG_RIGHT };
+
+struct SprsArray {
+    bool live = false, assembled = false;
+    int type = 0, elemsize = 0, optype = 0;
+    long idim = 0, jdim = 0;
+    std::vector<gaamd_sprs::Elem> pending;   // added here, not yet assembled
+    long long ilo = 0, nrows = 0;            // this rank's rows
+    long long nnz = 0, nnz_total = 0;        // entries here, entries on all ranks
+    int team = 1;                            // gaamd_spmv_team(nnz_total, idim)
+    std::vector<int> blocks;                 // the non-empty column blocks, ascending
+    std::vector<long long> start;            // where each begins in jdx / val
+    int *offs = nullptr;                     // HBM: [blocks][nrows + 1]
+    long long *dstart = nullptr;             // HBM: `start`
+    int *jdx = nullptr;                      // HBM: global columns
+    char *val = nullptr;                     // HBM: values
+};
+static std::vector<SprsArray> g_sprs;
+static long long g_sprs_routes[4] = {0, 0, 0, 0};   // x in place, x through scratch, y in place, y through scratch
+
+static SprsArray &sprs(int s_a, const char *what) {
+    if (s_a < 1 || s_a > (int)g_sprs.size() || !g_sprs[s_a - 1].live)
+        fatal("%s: invalid sparse array handle %d", what, s_a);
+    return g_sprs[s_a - 1];
+}
+
+static SprsArray &sprs_assembled(int s_a, const char *what) {
+    SprsArray &s = sprs(s_a, what);
+    if (!s.assembled) fatal("%s: the sparse array has not been assembled", what);
+    return s;
+}
+
+static void *sprs_dev_alloc(size_t bytes, const char *what) {
+    void *p = gaamd_dev_malloc(bytes);
+    if (!p) fatal("%s: no device memory for %zu bytes", what, bytes);
+    return p;
+}
+
+static void *sprs_upload(const void *host, size_t bytes, const char *what) {
+    void *p = sprs_dev_alloc(bytes, what);
+    if (gaamd_memcpy(p, host, bytes) != 0) fatal("%s: copying %zu bytes failed", what, bytes);
+    return p;
+}
+
+static void sprs_release(SprsArray &s) {
+    for (void *p : {(void *)s.offs, (void *)s.dstart, (void *)s.jdx, (void *)s.val})
+        if (p) gaamd_dev_free(p);
+    s.offs = nullptr;
+    s.dstart = nullptr;
+    s.jdx = nullptr;
+    s.val = nullptr;
+}
+
+static void sprs_release_all() {
+    for (SprsArray &s : g_sprs) {
+        sprs_release(s);
+        s = SprsArray();
+    }
+}
+
+// block b of the CSR: its offsets, and its place in jdx / val
+static const int *sprs_offs(const SprsArray &s, size_t b) { return s.offs + b * (size_t)(s.nrows + 1); }
+static char *sprs_val(const SprsArray &s, size_t b) { return s.val + s.start[b] * s.elemsize; }
+
+// a vector for a computing call: rank 1, `len` elements, the matrix's type, in HBM
+static void need_sprs_vector(const SprsArray &s, int g_v, long len, const char *what) {
+    const GArray &v = arr(g_v);
+    if (v.ndim != 1) fatal("%s: '%s' has rank %d, a vector of rank 1 is needed", what, v.name.c_str(), v.ndim);
+    if (v.type != s.type) fatal("%s: the type of '%s' differs from the sparse array's", what, v.name.c_str());
+    if (v.dims[0] != len) fatal("%s: '%s' has %ld elements, %ld are needed", what, v.name.c_str(), v.dims[0], len);
+    need_hbm(v, what);
+}
+
+// the columns this rank's entries can name: first column of its first non-empty block to the
+// last column of its last one (0-based, inclusive); false when it has no entry
+static bool sprs_col_span(const SprsArray &s, long long *lo, long long *hi) {
+    if (s.blocks.empty()) return false;
+    long long unused;
+    gaamd_sprs::range(s.jdim, world_size(), s.blocks.front(), lo, &unused);
+    gaamd_sprs::range(s.jdim, world_size(), s.blocks.back(), &unused, hi);
+    return true;
+}
+
+static void sprs_matvec(int s_a, int g_a, int g_v) {
+    const char *what = "NGA_Sprs_array_matvec_multiply";
+    SprsArray &s = sprs_assembled(s_a, what);
+    need_sprs_vector(s, g_a, s.jdim, what);
+    need_sprs_vector(s, g_v, s.idim, what);
+    if (g_a == g_v) fatal("%s: the vector and the product must be different arrays", what);
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_stat.numsprs[SP_MATVEC]++;
+    if (s.nrows > 0) {
+        long long c0 = 0, c1 = -1;
+        VecPart x;
+        if (sprs_col_span(s, &c0, &c1)) {
+            x = vec_part(g_a, (long)c0 + 1, (long)c1 + 1, V_READ, what);
+            g_sprs_routes[x.scratch.p ? 1 : 0]++;
+        }
+        VecPart y = vec_part(g_v, (long)s.ilo + 1, (long)(s.ilo + s.nrows), V_WRITE, what);
+        g_sprs_routes[y.scratch.p ? 3 : 2]++;
+        launched(gaamd_spmv(s.optype, s.nrows, (int)s.blocks.size(), s.offs, s.dstart, s.jdx, s.val, x.p, c0, y.p, s.team,
+                            gaamd_stream()),
+                 what);
+        vec_done(g_a, (long)c0 + 1, (long)c1 + 1, x, V_READ, what);
+        vec_done(g_v, (long)s.ilo + 1, (long)(s.ilo + s.nrows), y, V_WRITE, what);
+        g_stat.mathloc += (double)s.nnz * (2.0 * s.elemsize + 4) + (double)s.nrows * s.elemsize;
+    }
+    math_end(what);
+}
+
+// diag(d) S (left) or S diag(d) (right) on the values in place
+static void sprs_diag_multiply(bool left, int s_a, int g_d) {
+    const char *what = left ? "NGA_Sprs_array_diag_left_multiply" : "NGA_Sprs_array_diag_right_multiply";
+    SprsArray &s = sprs_assembled(s_a, what);
+    need_sprs_vector(s, g_d, left ? s.idim : s.jdim, what);
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_stat.numsprs[left ? SP_DIAG_LEFT : SP_DIAG_RIGHT]++;
+    long long lo = s.ilo, hi = s.ilo + s.nrows - 1;
+    if (s.nnz > 0 && (left || sprs_col_span(s, &lo, &hi))) {
+        VecPart d = vec_part(g_d, (long)lo + 1, (long)hi + 1, V_READ, what);
+        if (left) {
+            for (size_t b = 0; b < s.blocks.size(); b++)
+                launched(gaamd_sprs_scale_left(s.optype, s.nrows, sprs_offs(s, b), sprs_val(s, b), d.p, s.team,
+                                               gaamd_stream()),
+                         what);
+        } else {
+            launched(gaamd_sprs_scale_right(s.optype, s.nnz, s.jdx, s.val, d.p, lo, gaamd_stream()), what);
+        }
+        vec_done(g_d, (long)lo + 1, (long)hi + 1, d, V_READ, what);
+        g_stat.mathloc += (double)s.nnz * (3.0 * s.elemsize + (left ? 0 : 4));
+    }
+    math_end(what);
+}
+
+int NGA_Sprs_array_create(int idim, int jdim, int type) {
+    const char *what = "NGA_Sprs_array_create";
+    if (idim <= 0 || jdim <= 0) fatal("%s: dimensions %d x %d", what, idim, jdim);
+    SprsArray s;
+    s.type = type;
+    s.elemsize = type_size(type, &s.optype);
+    s.idim = idim;
+    s.jdim = jdim;
+    s.live = true;
+    g_sprs.push_back(s);
+    return (int)g_sprs.size();
+}
+
+void NGA_Sprs_array_add_element(int s_a, int idx, int jdx, void *val) {
+    const char *what = "NGA_Sprs_array_add_element";
+    SprsArray &s = sprs(s_a, what);
+    if (s.assembled) fatal("%s: the sparse array has been assembled already", what);
+    if (idx < 0 || idx >= s.idim || jdx < 0 || jdx >= s.jdim)
+        fatal("%s: element (%d, %d) outside the %ld x %ld array", what, idx, jdx, s.idim, s.jdim);
+    if (!val) fatal("%s: the value is missing", what);
+    gaamd_sprs::Elem e;
+    memset(&e, 0, sizeof(e));
+    e.i = idx;
+    e.j = jdx;
+    memcpy(e.v, val, (size_t)s.elemsize);
+    s.pending.push_back(e);
+}
+
+int NGA_Sprs_array_assemble(int s_a) {
+    const char *what = "NGA_Sprs_array_assemble";
+    SprsArray &s = sprs(s_a, what);
+    if (s.assembled) fatal("%s: the sparse array has been assembled already", what);
+    const int me = my_rank(), np = world_size();
+    typedef gaamd_sprs::Elem Elem;
+    // the np x np table of counts: row r holds what rank r sends to every owner
+    std::vector<long> table((size_t)np * np, 0);
+    for (const Elem &e : s.pending) table[(size_t)me * np + gaamd_sprs::owner(e.i, s.idim, np)]++;
+    exchange_slots(table);
+    std::vector<long long> total(np, 0);
+    s.nnz_total = 0;
+    for (int p = 0; p < np; p++) {
+        for (int r = 0; r < np; r++) total[p] += table[(size_t)r * np + p];
+        s.nnz_total += total[p];
+    }
+    for (int p = 0; p < np; p++)   // every rank holds the table: all end here
+        if (total[p] >= (1ll << 31)) fatal("%s: rank %d would hold %lld entries, 2^31 or more", what, p, total[p]);
+    // this rank's elements grouped by owner, insertion order kept
+    std::vector<size_t> pos(np, 0);
+    for (int p = 1; p < np; p++) pos[p] = pos[p - 1] + (size_t)table[(size_t)me * np + p - 1];
+    const std::vector<size_t> first = pos;
+    std::vector<Elem> out(s.pending.size());
+    for (const Elem &e : s.pending) out[pos[gaamd_sprs::owner(e.i, s.idim, np)]++] = e;
+    std::vector<Elem>().swap(s.pending);
+    // rank r's elements for owner p go after those of the ranks before r
+    std::vector<void *> seg(np, nullptr);
+    if (comex_malloc(seg.data(), (size_t)total[me] * sizeof(Elem), COMEX_GROUP_WORLD) != COMEX_SUCCESS)
+        fatal("%s: no segment for %lld incoming elements", what, total[me]);
+    comex_barrier(COMEX_GROUP_WORLD);
+    for (int p = 0; p < np; p++) {
+        const size_t n = (size_t)table[(size_t)me * np + p];
+        size_t before = 0;
+        for (int r = 0; r < me; r++) before += (size_t)table[(size_t)r * np + p];
+        const size_t piece = (1u << 30) / sizeof(Elem);   // comex_put counts bytes in an int
+        for (size_t k = 0; k < n; k += piece) {
+            const size_t c = std::min(piece, n - k);
+            if (comex_put(out.data() + first[p] + k, (char *)seg[p] + (before + k) * sizeof(Elem), (int)(c * sizeof(Elem)), p,
+                          COMEX_GROUP_WORLD) != COMEX_SUCCESS)
+                fatal("%s: sending %zu elements to rank %d failed", what, c, p);
+        }
+    }
+    comex_barrier(COMEX_GROUP_WORLD);   // fences: every element lies at its owner
+    std::vector<Elem> in((size_t)total[me]);
+    if (!in.empty()) {
+        if (gaamd_segment_kind(seg[me]) == 2) memcpy(in.data(), seg[me], in.size() * sizeof(Elem));
+        else if (gaamd_memcpy(in.data(), seg[me], in.size() * sizeof(Elem)) != 0) fatal("%s: reading the segment failed", what);
+    }
+    comex_free(seg[me], COMEX_GROUP_WORLD);
+    long long ihi;
+    gaamd_sprs::range(s.idim, np, me, &s.ilo, &ihi);
+    s.nrows = ihi - s.ilo + 1;
+    gaamd_sprs::BlockCsr csr;
+    gaamd_sprs::build(in, s.ilo, s.nrows, s.jdim, np, s.elemsize, csr);
+    s.nnz = (long long)in.size();
+    s.blocks = csr.blocks;
+    s.start = csr.start;
+    s.team = gaamd_spmv_team(s.nnz_total, s.idim);
+    if (s.nnz > 0) {
+        s.offs = (int *)sprs_upload(csr.offs.data(), csr.offs.size() * sizeof(int), what);
+        s.dstart = (long long *)sprs_upload(csr.start.data(), csr.start.size() * sizeof(long long), what);
+        s.jdx = (int *)sprs_upload(csr.jdx.data(), csr.jdx.size() * sizeof(int), what);
+        s.val = (char *)sprs_upload(csr.val.data(), csr.val.size(), what);
+    }
+    s.assembled = true;
+    g_stat.numsprs[SP_ASSEMBLE]++;
+    comex_barrier(COMEX_GROUP_WORLD);
+    return 1;
+}
+
+int NGA_Sprs_array_destroy(int s_a) {
+    SprsArray &s = sprs(s_a, "NGA_Sprs_array_destroy");
+    comex_barrier(COMEX_GROUP_WORLD);
+    sprs_release(s);
+    s = SprsArray();
+    return 1;
+}
+
+int NGA_Sprs_array_duplicate(int s_a) {
+    const char *what = "NGA_Sprs_array_duplicate";
+    (void)sprs(s_a, what);
+    comex_barrier(COMEX_GROUP_WORLD);   // no rank is still writing the values
+    SprsArray n = sprs(s_a, what);
+    if (n.assembled && n.nnz > 0) {
+        const size_t bytes[4] = {n.blocks.size() * (size_t)(n.nrows + 1) * sizeof(int), n.blocks.size() * sizeof(long long),
+                                 (size_t)n.nnz * sizeof(int), (size_t)n.nnz * (size_t)n.elemsize};
+        void *from[4] = {n.offs, n.dstart, n.jdx, n.val}, *to[4];
+        for (int k = 0; k < 4; k++) {
+            to[k] = sprs_dev_alloc(bytes[k], what);
+            if (gaamd_memcpy(to[k], from[k], bytes[k]) != 0) fatal("%s: copying %zu bytes failed", what, bytes[k]);
+        }
+        n.offs = (int *)to[0];
+        n.dstart = (long long *)to[1];
+        n.jdx = (int *)to[2];
+        n.val = (char *)to[3];
+    }
+    g_sprs.push_back(n);
+    return (int)g_sprs.size();
+}
+
+void gaamd_ga_sprs_range(long dim, int nproc, int iproc, long *lo, long *hi) {
+    long long l = 0, h = -1;
+    if (dim > 0 && nproc > 0 && iproc >= 0 && iproc < nproc) gaamd_sprs::range(dim, nproc, iproc, &l, &h);
+    *lo = (long)l;
+    *hi = (long)h;
+}
+
+void gaamd_ga_sprs_route_counts(long long counts[4]) { memcpy(counts, g_sprs_routes, sizeof(g_sprs_routes)); }
+
+static void sprs_distribution(long dim, int iproc, int *lo, int *hi, const char *what) {
+    if (iproc < 0 || iproc >= world_size()) fatal("%s: no rank %d", what, iproc);
+    long long l, h;
+    gaamd_sprs::range(dim, world_size(), iproc, &l, &h);
+    *lo = (int)l;
+    *hi = (int)h;
+}
+
+void NGA_Sprs_array_row_distribution(int s_a, int iproc, int *lo, int *hi) {
+    const char *what = "NGA_Sprs_array_row_distribution";
+    sprs_distribution(sprs(s_a, what).idim, iproc, lo, hi, what);
+}
+
+void NGA_Sprs_array_column_distribution(int s_a, int iproc, int *lo, int *hi) {
+    const char *what = "NGA_Sprs_array_column_distribution";
+    sprs_distribution(sprs(s_a, what).jdim, iproc, lo, hi, what);
+}
+
+void NGA_Sprs_array_col_block_list(int s_a, int **idx, int *n) {
+    const SprsArray &s = sprs_assembled(s_a, "NGA_Sprs_array_col_block_list");
+    *n = (int)s.blocks.size();
+    *idx = (int *)malloc(std::max<size_t>(1, s.blocks.size()) * sizeof(int));
+    std::copy(s.blocks.begin(), s.blocks.end(), *idx);
+}
+
+void NGA_Sprs_array_access_col_block(int s_a, int icol, int **idx, int **jdx, void **val) {
+    const char *what = "NGA_Sprs_array_access_col_block";
+    const SprsArray &s = sprs_assembled(s_a, what);
+    if (icol < 0 || icol >= world_size()) fatal("%s: no column block %d", what, icol);
+    *idx = nullptr;
+    *jdx = nullptr;
+    *val = nullptr;
+    const auto it = std::lower_bound(s.blocks.begin(), s.blocks.end(), icol);
+    if (it == s.blocks.end() || *it != icol) return;
+    const size_t b = (size_t)(it - s.blocks.begin());
+    *idx = const_cast<int *>(sprs_offs(s, b));
+    *jdx = s.jdx + s.start[b];
+    *val = sprs_val(s, b);
+}
+
+void NGA_Sprs_array_matvec_multiply(int s_a, int g_a, int g_v) { sprs_matvec(s_a, g_a, g_v); }
+
+void NGA_Sprs_array_get_diag(int s_a, int *g_d) {
+    const char *what = "NGA_Sprs_array_get_diag";
+    if (!g_d) fatal("%s: g_d is missing", what);
+    const int me = my_rank(), np = world_size();
+    GArray d;   // idim elements on the row cuts; allocate() zeroes it and syncs
+    {
+        const SprsArray &s = sprs_assembled(s_a, what);
+        d.type = s.type;
+        d.ndim = 1;
+        d.name = "sprs_diag";
+        d.elemsize = s.elemsize;
+        d.optype = s.optype;
+        d.dims[0] = s.idim;
+        d.nblock[0] = np;
+        for (int p = 0; p < np; p++) {
+            long long lo, hi;
+            gaamd_sprs::range(s.idim, np, p, &lo, &hi);
+            d.map[0].push_back((long)lo + 1);
+        }
+    }
+    comex_barrier(COMEX_GROUP_WORLD);
+    *g_d = allocate(d);
+    if (*g_d == 0) fatal("%s: no memory for the diagonal", what);
+    const SprsArray &s = sprs_assembled(s_a, what);
+    g_stat.numsprs[SP_GET_DIAG]++;
+    const auto it = std::lower_bound(s.blocks.begin(), s.blocks.end(), me);
+    if (s.nrows > 0 && it != s.blocks.end() && *it == me) {   // the rank's own diagonal column block only
+        const size_t b = (size_t)(it - s.blocks.begin());
+        launched(gaamd_sprs_diag(s.optype, GAAMD_DIAG_GET, s.nrows, sprs_offs(s, b), s.jdx + s.start[b], sprs_val(s, b),
+                                 s.ilo, arr(*g_d).ptr[me], nullptr, s.team, gaamd_stream()),
+                 what);
+        g_stat.mathloc += (double)s.nrows * (s.elemsize + 8);
+    }
+    math_end(what);
+}
+
+void NGA_Sprs_array_shift_diag(int s_a, void *shift) {
+    const char *what = "NGA_Sprs_array_shift_diag";
+    const SprsArray &s = sprs_assembled(s_a, what);
+    if (!shift) fatal("%s: the shift is missing", what);
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_stat.numsprs[SP_SHIFT_DIAG]++;
+    for (size_t b = 0; s.nrows > 0 && b < s.blocks.size(); b++)
+        launched(gaamd_sprs_diag(s.optype, GAAMD_DIAG_SHIFT, s.nrows, sprs_offs(s, b), s.jdx + s.start[b], sprs_val(s, b),
+                                 s.ilo, nullptr, shift, s.team, gaamd_stream()),
+                 what);
+    math_end(what);
+}
+
+void NGA_Sprs_array_scale(int s_a, void *scale) {
+    const char *what = "NGA_Sprs_array_scale";
+    const SprsArray &s = sprs_assembled(s_a, what);
+    if (!scale) fatal("%s: the factor is missing", what);
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_stat.numsprs[SP_SCALE]++;
+    if (s.nnz > 0) {
+        const long long count[1] = {s.nnz};
+        launched(gaamd_patch_scale(s.optype, scale, s.val, nullptr, count, 1, gaamd_stream()), what);
+        g_stat.mathloc += 2.0 * s.nnz * s.elemsize;
+    }
+    math_end(what);
+}
+
+void NGA_Sprs_array_diag_left_multiply(int s_a, int g_d) { sprs_diag_multiply(true, s_a, g_d); }
+void NGA_Sprs_array_diag_right_multiply(int s_a, int g_d) { sprs_diag_multiply(false, s_a, g_d); }
+
 void GA_Print_stats(void) {
     printf("[%d] GA on-device calls: fill %ld, scale %ld, add %ld, copy %ld, dot %ld; local bytes moved %.0f; "
            "gemm %ld\n",
@@ -1990,6 +2382,11 @@ void GA_Print_stats(void) {
            my_rank(), g_stat.numdiag, g_stat.numscalerows, g_stat.numscalecols, g_stat.numnorm1, g_stat.numnorminf);
     printf("[%d] GA sparse calls: enum %ld, scan_copy %ld, scan_add %ld, pack %ld, unpack %ld\n", my_rank(),
            g_stat.numenum, g_stat.numscancopy, g_stat.numscanadd, g_stat.numpack, g_stat.numunpack);
+    printf("[%d] GA sparse-array calls: assemble %ld, matvec %ld, get_diag %ld, shift_diag %ld, scale %ld, diag_left %ld, "
+           "diag_right %ld\n",
+           my_rank(), g_stat.numsprs[SP_ASSEMBLE], g_stat.numsprs[SP_MATVEC], g_stat.numsprs[SP_GET_DIAG],
+           g_stat.numsprs[SP_SHIFT_DIAG], g_stat.numsprs[SP_SCALE], g_stat.numsprs[SP_DIAG_LEFT],
+           g_stat.numsprs[SP_DIAG_RIGHT]);
 }
 
 }  // extern "C"

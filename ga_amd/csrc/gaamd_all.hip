@@ -11,6 +11,7 @@
 #include "gaamd_select.hip"
 #include "gaamd_matrix.hip"
 #include "gaamd_scan.hip"
+#include "gaamd_sprs.hip"
 #include "gaamd_gemm.hip"
 #include "gaamd_gemm_cplx.hip"
 #include "gaamd_transpose.hip"

@@ -179,6 +179,19 @@ int launch_mask_count(int mop, long long n, const void *msk, long long *count, h
 // pack (unpack == false): arr = src, other = packed (written); unpack: arr = dst (written), other = packed
 int launch_mask_move(bool unpack, int op, int mop, long long n, const void *arr, const void *msk, const void *other,
                      hipStream_t stream);
+// ---- GA's sparse arrays (gaamd_sprs.hip; ga_amd.h gaamd_spmv / _sprs_diag / _sprs_scale_left / _right): a block
+// CSR in HBM, nblk tables of nrows + 1 offsets (block b's at offs + b * (nrows + 1)) relative to start[b] in
+// jdx / val; the codes are the patch codes above (kPatchErrOp also: a team that is no power of two in 1..64) ----
+int spmv_team(long long nnz_total, long long rows);
+int launch_spmv(int op, long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+                const void *val, const void *x, long long x_first, void *y, int team, hipStream_t stream);
+// one column block; fn = kDiagGet (out[r] = the last stored (r, r)) or kDiagShift (every stored (r, r) += *shift)
+int launch_sprs_diag(int op, int fn, long long nrows, const int *offs, const int *jdx, void *val, long long diag_first,
+                     void *out, const void *shift, int team, hipStream_t stream);
+int launch_sprs_scale_left(int op, long long nrows, const int *offs, void *val, const void *d, int team,
+                           hipStream_t stream);
+int launch_sprs_scale_right(int op, long long n, const int *jdx, void *val, const void *d, long long d_first,
+                            hipStream_t stream);
 struct PatchPlan;
 // launch_patch_add's checks without a launch (no device): 0 launch, 1 nothing to do, < 0 error;
 // plan[0..3] = {vector width, row levels after merging, rows, vectors per row}

@@ -165,6 +165,27 @@ int gaamd_mask_unpack(int op, int mop, long long n, const void *packed, const vo
     return launch_mask_move(true, op, mop, n, dst, msk, packed, stream_of(stream));
 }
 
+int gaamd_spmv_team(long long nnz_total, long long rows) { return spmv_team(nnz_total, rows); }
+
+int gaamd_spmv(int op, long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+               const void *val, const void *x, long long x_first, void *y, int team, void *stream) {
+    return launch_spmv(op, nrows, nblk, offs, start, jdx, val, x, x_first, y, team, stream_of(stream));
+}
+
+int gaamd_sprs_diag(int op, int fn, long long nrows, const int *offs, const int *jdx, void *val, long long diag_first,
+                    void *out, const void *shift, int team, void *stream) {
+    return launch_sprs_diag(op, fn, nrows, offs, jdx, val, diag_first, out, shift, team, stream_of(stream));
+}
+
+int gaamd_sprs_scale_left(int op, long long nrows, const int *offs, void *val, const void *d, int team, void *stream) {
+    return launch_sprs_scale_left(op, nrows, offs, val, d, team, stream_of(stream));
+}
+
+int gaamd_sprs_scale_right(int op, long long n, const int *jdx, void *val, const void *d, long long d_first,
+                           void *stream) {
+    return launch_sprs_scale_right(op, n, jdx, val, d, d_first, stream_of(stream));
+}
+
 int gaamd_gemm(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
                const void *a, long long lda, const void *b, long long ldb, const void *beta, void *c, long long ldc,
                void *stream) {

@@ -327,6 +327,91 @@ void GA_Scan_copy(int g_src, int g_dst, int g_msk, int lo, int hi);
 void GA_Scan_add(int g_src, int g_dst, int g_msk, int lo, int hi, int excl);
 void GA_Pack(int g_src, int g_dst, int g_msk, int lo, int hi, int *icount);
 void GA_Unpack(int g_src, int g_dst, int g_msk, int lo, int hi, int *icount);
+/* Sparse arrays (global/src/ga.h:355-382 -> global/src/sparse.array.c), the 32-bit-index forms: a
+   distributed idim x jdim sparse matrix of any of the six types, held as a block CSR in each rank's
+   HBM, and its product with a distributed vector.
+   Distribution: row i belongs to rank min((i * nproc) / idim, nproc - 1), column j to column block
+   min((j * nproc) / jdim, nproc - 1), in 64-bit arithmetic (sparse.array.c:326, 524).
+   NGA_Sprs_array_row_distribution / _column_distribution return that set for iproc as [lo, hi],
+   zero-based and inclusive; a rank that owns nothing gets hi = lo - 1.  gaamd_ga_sprs_range is the
+   same rule for any dim and nproc, host-only (no GPU, no GA_Initialize).
+   Handles are a name space of their own, counted from 1.  A sparse array holds NO global array
+   inside: its CSR lies in plain HBM allocations of the rank, so gaamd_ga_live_arrays() does not
+   change from NGA_Sprs_array_create to NGA_Sprs_array_destroy (the incoming segment of assemble is
+   freed before it returns).  The array NGA_Sprs_array_get_diag returns is the caller's to destroy.
+     s_a = NGA_Sprs_array_create(idim, jdim, type)        local bookkeeping, the same call on every rank
+     NGA_Sprs_array_add_element(s_a, i, j, &val)          local; any rank may add any (i, j), zero-based
+     NGA_Sprs_array_assemble(s_a)                         collective; returns 1
+   Assembly, an order contract (the reference places elements by pnga_read_inc, in arrival order):
+   the ranks exchange the nproc x nproc table of counts; rank r's elements for owner p are stored
+   after those of the ranks before r, in insertion order; the owner then stable-sorts what it holds
+   by column block, row and column.  Duplicates of one (i, j) stay separate entries, in source-rank
+   then insertion order.  The sort runs on the host and the result is uploaded once.
+   Layout, as NGA_Sprs_array_access_col_block(s_a, icol, &idx, &jdx, &val) shows it: per non-empty
+   column block, idx holds the rank's row count + 1 row offsets relative to the block's start, jdx
+   global zero-based column indices and val the values; entries within a row are in ascending
+   column order (the reference's TODO at sparse.array.c:764).  All three are HBM ADDRESSES like
+   NGA_Access's, for kernels, not for host dereference; all three are NULL for an empty block.
+   NGA_Sprs_array_col_block_list(s_a, &idx, &n) returns the non-empty blocks, ascending, in a
+   malloc'ed list the caller frees.  NGA_Sprs_array_duplicate copies the matrix as it stands (the
+   copy outlives the original); NGA_Sprs_array_destroy frees it.  Both collective.
+     NGA_Sprs_array_matvec_multiply(s_a, g_a, g_v)        v = S a
+   g_a has rank 1, jdim elements and the matrix's type, g_v rank 1, idim elements and that type;
+   REGULAR or irregular block maps, which need not match the matrix's cuts or each other.  The owner
+   of a row block computes with gaamd_spmv (ga_amd.h).  It needs g_a over the span of its non-empty
+   column blocks: used in place where that span lies in its own block of g_a, otherwise fetched into
+   HBM scratch with NGA_Get's path.  It writes g_v for its rows in place where they lie in its own
+   block of g_v, otherwise through scratch and NGA_Put's path, complete at the owner before the
+   closing sync; the scratch is freed before return.  g_v is OVERWRITTEN (rows without entries give
+   0; the reference's macro assigns per column block).  A rank without rows launches nothing and
+   takes part in the syncs.  gaamd_ga_sprs_route_counts: {x in place, x through scratch, y in place,
+   y through scratch} taken so far on this rank.
+   Arithmetic contract: gaamd_spmv's -- per entry one product and one add, never fused; integers wrap;
+   the true complex product re = a.re*x.re - a.im*x.im, im = a.re*x.im + a.im*x.re (a stated
+   departure: the reference's complex macro reads the vector where it means the matrix value); the
+   entries of a row over all column blocks in ascending order are ONE list, summed by a team of W
+   lanes, lane L taking e_L, e_{L+W}, ... from +0 and the partials combined by a fixed butterfly.
+   W = gaamd_spmv_team(entries of the whole matrix, idim) depends on global counts only.
+   Consequence: for a matrix without duplicate (i, j), or whose duplicates keep their relative
+   order, the product is the same bits on every call, on any number of ranks, and under any block
+   maps of g_a and g_v: the column blocks change with the rank count, the concatenated list does not.
+   The other calls, the reference's expressions as kernels on the block CSR in place (ga_amd.h
+   gaamd_sprs_diag, gaamd_sprs_scale_left / _right, gaamd_patch_scale):
+     NGA_Sprs_array_get_diag(s_a, &g_d)       a new 1-D array of idim elements on the row cuts, zeroed,
+                                              then d_i = a_ii where stored -- from the rank's own
+                                              diagonal column block only (sparse.array.c:1646-1693);
+                                              of duplicates the last in storage order
+     NGA_Sprs_array_shift_diag(s_a, &shift)   a_ii += shift on EVERY stored (i, i); none is created;
+                                              complex part by part
+     NGA_Sprs_array_scale(s_a, &scale)        every value *= scale, as GA_Scale
+     NGA_Sprs_array_diag_left_multiply(s_a, g_d)    a_ij = d_i * a_ij, d of idim elements
+     NGA_Sprs_array_diag_right_multiply(s_a, g_d)   a_ij = d_j * a_ij, d of jdim elements
+   both true complex products (sparse.array.c:1754-1770), unlike GA_Scale_rows; d may have any
+   block map and is obtained as g_a is.
+   Aborts through GA_Error -- the collective calls on every rank, before the first sync or launch:
+   idim or jdim <= 0 or an unknown type; add_element after assemble, with an index out of range or
+   without a value; any computing call, access_col_block and col_block_list before assemble; a
+   second assemble; a handle that is not live; a vector of the wrong rank, length or type, or in a
+   host segment; g_a == g_v; a rank that would hold 2^31 entries or more; a missing shift, scale or
+   g_d.  Not provided: the *64 forms, matmat_multiply, sprsdns / dnssprs_multiply, get_block,
+   get_column, create_from_dense / _sparse, export, count_sketch. */
+int NGA_Sprs_array_create(int idim, int jdim, int type);
+void NGA_Sprs_array_add_element(int s_a, int idx, int jdx, void *val);
+int NGA_Sprs_array_assemble(int s_a);
+int NGA_Sprs_array_destroy(int s_a);
+int NGA_Sprs_array_duplicate(int s_a);
+void NGA_Sprs_array_row_distribution(int s_a, int iproc, int *lo, int *hi);
+void NGA_Sprs_array_column_distribution(int s_a, int iproc, int *lo, int *hi);
+void NGA_Sprs_array_col_block_list(int s_a, int **idx, int *n);
+void NGA_Sprs_array_access_col_block(int s_a, int icol, int **idx, int **jdx, void **val);
+void NGA_Sprs_array_matvec_multiply(int s_a, int g_a, int g_v);
+void NGA_Sprs_array_get_diag(int s_a, int *g_d);
+void NGA_Sprs_array_shift_diag(int s_a, void *shift);
+void NGA_Sprs_array_scale(int s_a, void *scale);
+void NGA_Sprs_array_diag_left_multiply(int s_a, int g_d);
+void NGA_Sprs_array_diag_right_multiply(int s_a, int g_d);
+void gaamd_ga_sprs_range(long dim, int nproc, int iproc, long *lo, long *hi);
+void gaamd_ga_sprs_route_counts(long long counts[4]);
 /* global arrays alive on this rank (temporaries of the general path are destroyed
    before their call returns) */
 int gaamd_ga_live_arrays(void);

@@ -294,6 +294,52 @@ int gaamd_scan(int op, int fn, int mop, long long n, const void *src, const void
 int gaamd_mask_count(int mop, long long n, const void *msk, long long *count /* host */, void *stream);
 int gaamd_mask_pack(int op, int mop, long long n, const void *src, const void *msk, void *packed, void *stream);
 int gaamd_mask_unpack(int op, int mop, long long n, const void *packed, const void *msk, void *dst, void *stream);
+/* GA's sparse arrays (global/src/sparse.array.c) as kernels on a block CSR in HBM; the kernels
+ * under NGA_Sprs_array_matvec_multiply, _get_diag, _shift_diag, _diag_left_multiply and
+ * _diag_right_multiply (ga.h).  op = COMEX_ACC_* names the element type, all six.
+ * Layout: the rows of one rank, cut into nblk column blocks.  Block b has a table of nrows + 1
+ * row offsets (int) at offs + b * (nrows + 1); they are relative to start[b], the place where the
+ * block begins in jdx (int, GLOBAL column indices) and val (elements).  offs, start (long long,
+ * nblk of them), jdx, val, x, y and d are HBM addresses.  The entries of a row, over the blocks in
+ * ascending order, form one list e_0 .. e_{c-1}.
+ *   gaamd_spmv   y[r] = sum over the row's list of val * x[jdx - x_first], r < nrows; x_first is
+ *                the global column of x[0].  y is overwritten; a row without entries gives +0.
+ * Arithmetic and order (a contract): per entry one product, then one add, never fused.  Integers
+ * wrap (unsigned arithmetic).  A complex product is re = a.re*x.re - a.im*x.im,
+ * im = a.re*x.im + a.im*x.re, and the sum is taken part by part.  A team of W = `team` lanes
+ * computes a row: lane L sums e_L, e_{L+W}, ... sequentially from +0, and the W partials p are
+ * combined by the butterfly p[l] = p[l] + p[l ^ s] for s = 1, 2, .. W / 2 (lanes past the row's
+ * end hold +0).  The same arrays and team therefore give the same bits on every call, however the
+ * list is cut into blocks.  Nothing of x is read but the elements the entries name.
+ *   gaamd_spmv_team(nnz_total, rows)   the team the GA layer uses: the smallest power of two W
+ *                with 2 * W * rows >= nnz_total, 1 <= W <= 64 (1 when either count is < 1); it grows
+ *                with nnz_total and shrinks with rows, and knows nothing of ranks.
+ *   gaamd_sprs_diag   ONE column block (offs its table, jdx / val from its start), row r being
+ *                global row diag_first + r:  fn = GAAMD_DIAG_GET: out[r] = the value of the last
+ *                entry of row r, in storage order, whose column is diag_first + r; out[r] is left
+ *                alone where there is none.  fn = GAAMD_DIAG_SHIFT: every such entry += *shift
+ *                (host, one element), complex part by part; no entry is created.
+ *   gaamd_sprs_scale_left    one column block: val[k] = d[r] * val[k] for the entries k of row r
+ *   gaamd_sprs_scale_right   n entries: val[k] = d[jdx[k] - d_first] * val[k]
+ *                both the true complex product, re = d.re*v.re - d.im*v.im, im = d.re*v.im + d.im*v.re
+ *                (sparse.array.c:1754-1770), unlike gaamd_scale_rows.
+ * One team per row, 256 / W rows per workgroup, teams packed into wave64; rows are walked with a
+ * 64-bit stride loop, and every offset into offs, jdx, val, x, y is 64-bit.  For W >= 2 consecutive
+ * lanes read consecutive jdx / val.  The cross-lane step is ds_bpermute_b32; no atomics, no LDS,
+ * no scratch (k_spmv: at most 30 VGPRs).
+ * Negative codes, all before any launch, in this order: -3 a negative nrows, nblk or n; -4 an
+ * unknown op or fn, or a team that is no power of two in 1..64; then nrows == 0 (n == 0): 0 and
+ * no launch; -5 a missing pointer (gaamd_spmv with nblk == 0 needs y only); -7 nrows above 2^40
+ * (n from 2^39); -8 val, x, y, d or out below the element's alignment, start below 8, offs or jdx
+ * below 4. */
+int gaamd_spmv_team(long long nnz_total, long long rows);
+int gaamd_spmv(int op, long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+               const void *val, const void *x, long long x_first, void *y, int team, void *stream);
+int gaamd_sprs_diag(int op, int fn, long long nrows, const int *offs, const int *jdx, void *val, long long diag_first,
+                    void *out, const void *shift /* host, one element */, int team, void *stream);
+int gaamd_sprs_scale_left(int op, long long nrows, const int *offs, void *val, const void *d, int team, void *stream);
+int gaamd_sprs_scale_right(int op, long long n, const int *jdx, void *val, const void *d, long long d_first,
+                           void *stream);
 /* Row-major GEMM on the gfx950 matrix cores, for op = COMEX_ACC_DBL (v_mfma_f64_16x16x4_f64)
  * and COMEX_ACC_FLT (v_mfma_f32_16x16x4_f32); the kernel under GA_Dgemm / GA_Sgemm (ga.h):
  *   C[i][j] = alpha * sum_k op(A)[i][k] * op(B)[k][j] + beta * C[i][j],  i < m, j < n, kk < k
