@@ -342,6 +342,35 @@ def sprs_scale_right(op, n, jdx, val, d, d_first, stream=None):
     return lib().gaamd_sprs_scale_right(op, n, _vp(jdx), _vp(val), _vp(d), d_first, stream)
 
 
+def spmm(op, nrows, nblk, offs, start, jdx, val, b, ldb, b_first, n, c, ldc, stream=None):
+    """c[r][j] = sum of val * b[jdx - b_first][j] over row r's entries, sequentially in list order; j < n"""
+    return lib().gaamd_spmm(op, nrows, nblk, _vp(offs), _vp(start), _vp(jdx), _vp(val), _vp(b), ldb, b_first, n, _vp(c),
+                            ldc, stream)
+
+
+def dense_row_counts(op, rows, cols, a, lda, row_first, col_first, counts, stream=None):
+    """counts[r] = the elements of row r that are != 0 or on the global diagonal"""
+    return lib().gaamd_dense_row_counts(op, rows, cols, _vp(a), lda, row_first, col_first, _vp(counts), stream)
+
+
+def dense_to_csr(op, rows, cols, a, lda, row_first, col_first, offs, jdx, val, stream=None):
+    """the kept elements of row r to jdx (global columns) / val at offs[r], in ascending column order"""
+    return lib().gaamd_dense_to_csr(op, rows, cols, _vp(a), lda, row_first, col_first, _vp(offs), _vp(jdx), _vp(val),
+                                    stream)
+
+
+def csr_to_dense(op, nrows, cols, offs, jdx, val, col_first, out, ldo, stream=None):
+    """one column block: out[r][jdx - col_first] = val, of duplicates the last; the caller zeroes out"""
+    return lib().gaamd_csr_to_dense(op, nrows, cols, _vp(offs), _vp(jdx), _vp(val), col_first, _vp(out), ldo, stream)
+
+
+def spmm_route_counts():
+    """{B in place, B through scratch, C in place, C through scratch} of NGA_Sprs_array_sprsdns_multiply so far"""
+    out = (ctypes.c_longlong * 4)()
+    lib().gaamd_ga_spmm_route_counts(out)
+    return list(out)
+
+
 def sprs_range(dim, nproc, iproc):
     """(lo, hi) of the indices of a dimension of `dim` that rank iproc of nproc owns (host only)"""
     lo, hi = ctypes.c_long(0), ctypes.c_long(0)

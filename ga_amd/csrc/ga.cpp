@@ -2363,6 +2363,238 @@ void NGA_Sprs_array_scale(int s_a, void *scale) {
 void NGA_Sprs_array_diag_left_multiply(int s_a, int g_d) { sprs_diag_multiply(true, s_a, g_d); }
 void NGA_Sprs_array_diag_right_multiply(int s_a, int g_d) { sprs_diag_multiply(false, s_a, g_d); }
 
+// ---- sparse x dense, dense -> sparse, sparse -> dense (sparse.array.c:3222-3840) ----------------
+enum SpmmCall { SM_SPRSDNS, SM_FROM_DENSE, SM_FROM_SPARSE };
+static long g_spmm_calls[3] = {0, 0, 0};
+static long long g_spmm_routes[4] = {0, 0, 0, 0};   // B in place, B through scratch, C in place, C through scratch
+constexpr size_t kSpmmPanelBytes = (size_t)1 << 28;   // the most one scratch side of a panel holds
+
+void gaamd_ga_spmm_route_counts(long long counts[4]) { memcpy(counts, g_spmm_routes, sizeof(g_spmm_routes)); }
+
+// a dense idim x ncols array on the sparse array's row cuts: one block of full rows per rank that
+// owns rows (sparse.array.c:3669-3696), so block k lies on rank k; not yet allocated
+static GArray sprs_row_array(const SprsArray &s, long ncols, const char *name) {
+    GArray d;
+    d.type = s.type;
+    d.ndim = 2;
+    d.name = name;
+    d.elemsize = s.elemsize;
+    d.optype = s.optype;
+    d.dims[0] = ncols;
+    d.dims[1] = s.idim;
+    d.nblock[0] = 1;
+    d.map[0].push_back(1);
+    for (int p = 0; p < world_size(); p++) {
+        long long lo, hi;
+        gaamd_sprs::range(s.idim, world_size(), p, &lo, &hi);
+        if (hi >= lo) d.map[1].push_back((long)lo + 1);
+    }
+    d.nblock[1] = (int)d.map[1].size();
+    return d;
+}
+
+// rows [r0, r1] x columns [j0, j1] (0-based, inclusive) of the 2-D array g for this rank's kernel: in
+// place (ld the block's) where the rank's own block covers rows [r0, r1] x ALL columns, else scratch
+// of the panel (ld its width), filled by a get for V_READ
+struct MatPart {
+    char *p = nullptr;
+    long long ld = 0;
+    Scratch scratch;
+};
+static bool mat_in_place(int g, long long r0, long long r1) {
+    const GArray &a = arr(g);
+    Patch p;
+    p.lo[0] = 1;
+    p.hi[0] = a.dims[0];
+    p.lo[1] = (long)r0 + 1;
+    p.hi[1] = (long)r1 + 1;
+    const Sub s = own_sub(a, p);
+    return s.any && s.count[0] == a.dims[0] && s.count[1] == r1 - r0 + 1;
+}
+static MatPart mat_part(int g, bool in_place, long long r0, long long r1, long long j0, long long j1, VecUse use,
+                        const char *what) {
+    MatPart r;
+    GArray &a = arr(g);
+    Patch p;
+    p.lo[0] = (long)j0 + 1;
+    p.hi[0] = (long)j1 + 1;
+    p.lo[1] = (long)r0 + 1;
+    p.hi[1] = (long)r1 + 1;
+    if (in_place) {
+        const Sub s = own_sub(a, p);
+        r.p = s.p;
+        r.ld = s.ext[0];
+        return r;
+    }
+    r.ld = j1 - j0 + 1;
+    r.p = (char *)r.scratch.alloc((size_t)(r1 - r0 + 1) * (size_t)r.ld * a.elemsize);
+    if (!r.p) fatal("%s: no device memory for %lld x %lld elements of scratch", what, r1 - r0 + 1, r.ld);
+    const long ld[1] = {(long)r.ld};
+    if (use == V_READ) patch_op(GA_GET, g, p.lo, p.hi, r.p, ld, nullptr);
+    return r;
+}
+// the kernel has written the scratch: store it, complete at its owner, and free it
+static void mat_done(int g, long long r0, long long r1, long long j0, long long j1, MatPart &r, VecUse use, const char *what) {
+    stream_wait(what);
+    if (!r.scratch.p) return;
+    if (use == V_WRITE) {
+        const long lo[2] = {(long)j0 + 1, (long)r0 + 1}, hi[2] = {(long)j1 + 1, (long)r1 + 1}, ld[1] = {(long)r.ld};
+        patch_op(GA_PUT, g, lo, hi, r.scratch.p, ld, nullptr);
+        comex_fence_all(COMEX_GROUP_WORLD);
+    }
+    r.scratch.free();
+}
+
+int NGA_Sprs_array_sprsdns_multiply(int s_a, int g_b) {
+    const char *what = "NGA_Sprs_array_sprsdns_multiply";
+    SprsArray &s = sprs_assembled(s_a, what);
+    long n;
+    {
+        const GArray &b = arr(g_b);
+        if (b.ndim != 2) fatal("%s: '%s' has rank %d, a matrix of rank 2 is needed", what, b.name.c_str(), b.ndim);
+        if (b.type != s.type) fatal("%s: the type of '%s' differs from the sparse array's", what, b.name.c_str());
+        if (b.dims[1] != s.jdim) fatal("%s: '%s' has %ld rows, %ld are needed", what, b.name.c_str(), b.dims[1], s.jdim);
+        need_hbm(b, what);
+        n = b.dims[0];
+    }
+    GArray c = sprs_row_array(s, n, "sprs_dns_product");
+    comex_barrier(COMEX_GROUP_WORLD);
+    const int g_c = allocate(c);   // zeroes and syncs
+    if (g_c == 0) fatal("%s: no memory for the product", what);
+    g_spmm_calls[SM_SPRSDNS]++;
+    if (s.nrows > 0) {
+        const long long r0 = s.ilo, r1 = s.ilo + s.nrows - 1;
+        long long c0 = 0, c1 = -1;
+        const bool has_b = sprs_col_span(s, &c0, &c1);
+        const bool b_own = has_b && mat_in_place(g_b, c0, c1), c_own = mat_in_place(g_c, r0, r1);
+        if (has_b) g_spmm_routes[b_own ? 0 : 1]++;
+        g_spmm_routes[c_own ? 2 : 3]++;
+        // panels of columns bound each scratch side by kSpmmPanelBytes (one column at the least)
+        long long rows_max = 0;
+        if (has_b && !b_own) rows_max = c1 - c0 + 1;
+        if (!c_own) rows_max = std::max(rows_max, s.nrows);
+        long long pw = n;
+        if (rows_max > 0) pw = std::max<long long>(1, std::min<long long>(n, (long long)(kSpmmPanelBytes / s.elemsize) / rows_max));
+        for (long long j0 = 0; j0 < n; j0 += pw) {
+            const long long j1 = std::min<long long>(n, j0 + pw) - 1;
+            MatPart bp;
+            if (has_b) bp = mat_part(g_b, b_own, c0, c1, j0, j1, V_READ, what);
+            MatPart cp = mat_part(g_c, c_own, r0, r1, j0, j1, V_WRITE, what);
+            launched(gaamd_spmm(s.optype, s.nrows, (int)s.blocks.size(), s.offs, s.dstart, s.jdx, s.val, bp.p, bp.ld, c0,
+                                j1 - j0 + 1, cp.p, cp.ld, gaamd_stream()),
+                     what);
+            mat_done(g_c, r0, r1, j0, j1, cp, V_WRITE, what);
+            mat_done(g_b, c0, c1, j0, j1, bp, V_READ, what);
+        }
+        g_stat.mathloc += (double)s.nnz * (s.elemsize + 4) + ((double)s.nnz + (double)s.nrows) * (double)n * s.elemsize;
+    }
+    math_end(what);
+    return g_c;
+}
+
+int NGA_Sprs_array_create_from_dense(int g_a) {
+    const char *what = "NGA_Sprs_array_create_from_dense";
+    const int me = my_rank(), np = world_size();
+    int type, optype, esz;
+    long idim, jdim;
+    {
+        const GArray &a = arr(g_a);
+        if (a.ndim != 2) fatal("%s: '%s' has rank %d, a matrix of rank 2 is needed", what, a.name.c_str(), a.ndim);
+        need_hbm(a, what);
+        if (a.dims[0] >= (1l << 31) || a.dims[1] >= (1l << 31)) fatal("%s: a dimension of 2^31 or more", what);
+        type = a.type;
+        optype = a.optype;
+        esz = a.elemsize;
+        idim = a.dims[1];
+        jdim = a.dims[0];
+    }
+    comex_barrier(COMEX_GROUP_WORLD);   // no rank is still writing g_a
+    g_spmm_calls[SM_FROM_DENSE]++;
+    const Sub sa = own_sub(arr(g_a), Patch(arr(g_a), nullptr, nullptr));
+    const long long rows = sa.any ? sa.count[1] : 0, cols = sa.any ? sa.count[0] : 0;
+    std::vector<int> offs((size_t)rows + 1, 0);
+    Scratch d_offs;
+    long long kept = 0;
+    if (rows > 0) {
+        if (!d_offs.alloc(offs.size() * sizeof(int))) fatal("%s: no device memory for %lld row counts", what, rows);
+        launched(gaamd_dense_row_counts(optype, rows, cols, sa.p, sa.ext[0], sa.plo[1] - 1, sa.plo[0] - 1, (int *)d_offs.p,
+                                        gaamd_stream()),
+                 what);
+        stream_wait(what);
+        if (gaamd_memcpy(offs.data() + 1, d_offs.p, (size_t)rows * sizeof(int)) != 0) fatal("%s: reading the counts failed", what);
+        for (long long r = 0; r < rows; r++) {   // the exclusive prefix sums, in 64 bits
+            const long long c = offs[(size_t)r + 1];
+            offs[(size_t)r] = (int)std::min<long long>(kept, INT32_MAX);
+            kept += c;
+        }
+        offs[(size_t)rows] = (int)std::min<long long>(kept, INT32_MAX);
+        g_stat.mathloc += sa.bytes;
+    }
+    std::vector<long> totals((size_t)np, 0);
+    totals[(size_t)me] = (long)kept;
+    exchange_slots(totals);
+    for (int p = 0; p < np; p++)   // every rank holds the totals: all end here, before any is stored
+        if (totals[(size_t)p] >= (1l << 31)) fatal("%s: rank %d would keep %ld entries, 2^31 or more", what, p, totals[(size_t)p]);
+    const int s_new = NGA_Sprs_array_create((int)idim, (int)jdim, type);
+    if (kept > 0) {
+        Scratch d_jdx, d_val;
+        if (!d_jdx.alloc((size_t)kept * sizeof(int)) || !d_val.alloc((size_t)kept * (size_t)esz))
+            fatal("%s: no device memory for %lld kept elements", what, kept);
+        if (gaamd_memcpy(d_offs.p, offs.data(), offs.size() * sizeof(int)) != 0) fatal("%s: copying the offsets failed", what);
+        launched(gaamd_dense_to_csr(optype, rows, cols, sa.p, sa.ext[0], sa.plo[1] - 1, sa.plo[0] - 1, (const int *)d_offs.p,
+                                    (int *)d_jdx.p, d_val.p, gaamd_stream()),
+                 what);
+        stream_wait(what);
+        std::vector<int> jdx((size_t)kept);
+        std::vector<unsigned char> val((size_t)kept * (size_t)esz);
+        if (gaamd_memcpy(jdx.data(), d_jdx.p, jdx.size() * sizeof(int)) != 0 || gaamd_memcpy(val.data(), d_val.p, val.size()) != 0)
+            fatal("%s: reading the kept elements failed", what);
+        g_stat.mathloc += sa.bytes + (double)kept * (esz + 4);
+        std::vector<gaamd_sprs::Elem> &pending = g_sprs[(size_t)s_new - 1].pending;
+        pending.resize((size_t)kept);
+        for (long long r = 0; r < rows; r++)
+            for (int k = offs[(size_t)r]; k < offs[(size_t)r + 1]; k++) {
+                gaamd_sprs::Elem &e = pending[(size_t)k];
+                memset(&e, 0, sizeof(e));
+                e.i = (int32_t)(sa.plo[1] - 1 + r);
+                e.j = jdx[(size_t)k];
+                memcpy(e.v, val.data() + (size_t)k * (size_t)esz, (size_t)esz);
+            }
+    }
+    NGA_Sprs_array_assemble(s_new);   // syncs; counted as an assemble too
+    return s_new;
+}
+
+int NGA_Sprs_array_create_from_sparse(int s_a) {
+    const char *what = "NGA_Sprs_array_create_from_sparse";
+    SprsArray &s = sprs_assembled(s_a, what);
+    GArray d = sprs_row_array(s, s.jdim, "sprs_dense");
+    comex_barrier(COMEX_GROUP_WORLD);
+    const int g_d = allocate(d);   // zeroes and syncs
+    if (g_d == 0) fatal("%s: no memory for the dense array", what);
+    g_spmm_calls[SM_FROM_SPARSE]++;
+    if (s.nrows > 0 && s.nnz > 0) {
+        const long long r0 = s.ilo, r1 = s.ilo + s.nrows - 1;
+        const bool own = mat_in_place(g_d, r0, r1);
+        // rows that lie in another rank's block: full-width panels of rows, zeroed, scattered and put
+        const long long rows_max = own ? s.nrows : std::max<long long>(1, (long long)(kSpmmPanelBytes / s.elemsize) / s.jdim);
+        for (long long q0 = 0; q0 < s.nrows; q0 += rows_max) {
+            const long long q1 = std::min<long long>(s.nrows, q0 + rows_max) - 1;
+            MatPart out = mat_part(g_d, own, r0 + q0, r0 + q1, 0, s.jdim - 1, V_WRITE, what);
+            if (!own && gaamd_memset(out.p, 0, (size_t)(q1 - q0 + 1) * (size_t)s.jdim * s.elemsize) != 0)
+                fatal("%s: zeroing the scratch failed", what);
+            for (size_t b = 0; b < s.blocks.size(); b++)
+                launched(gaamd_csr_to_dense(s.optype, q1 - q0 + 1, s.jdim, sprs_offs(s, b) + q0, s.jdx + s.start[b],
+                                            sprs_val(s, b), 0, out.p, out.ld, gaamd_stream()),
+                         what);
+            mat_done(g_d, r0 + q0, r0 + q1, 0, s.jdim - 1, out, V_WRITE, what);
+        }
+        g_stat.mathloc += (double)s.nnz * (2.0 * s.elemsize + 4);
+    }
+    math_end(what);
+    return g_d;
+}
+
 void GA_Print_stats(void) {
     printf("[%d] GA on-device calls: fill %ld, scale %ld, add %ld, copy %ld, dot %ld; local bytes moved %.0f; "
            "gemm %ld\n",
@@ -2387,6 +2619,8 @@ void GA_Print_stats(void) {
            my_rank(), g_stat.numsprs[SP_ASSEMBLE], g_stat.numsprs[SP_MATVEC], g_stat.numsprs[SP_GET_DIAG],
            g_stat.numsprs[SP_SHIFT_DIAG], g_stat.numsprs[SP_SCALE], g_stat.numsprs[SP_DIAG_LEFT],
            g_stat.numsprs[SP_DIAG_RIGHT]);
+    printf("[%d] GA sparse-product calls: sprsdns %ld, from_dense %ld, from_sparse %ld\n", my_rank(),
+           g_spmm_calls[SM_SPRSDNS], g_spmm_calls[SM_FROM_DENSE], g_spmm_calls[SM_FROM_SPARSE]);
 }
 
 }  // extern "C"

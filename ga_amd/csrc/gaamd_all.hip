@@ -12,6 +12,7 @@
 #include "gaamd_matrix.hip"
 #include "gaamd_scan.hip"
 #include "gaamd_sprs.hip"
+#include "gaamd_spmm.hip"
 #include "gaamd_gemm.hip"
 #include "gaamd_gemm_cplx.hip"
 #include "gaamd_transpose.hip"

@@ -192,6 +192,18 @@ int launch_sprs_scale_left(int op, long long nrows, const int *offs, void *val, 
                            hipStream_t stream);
 int launch_sprs_scale_right(int op, long long n, const int *jdx, void *val, const void *d, long long d_first,
                             hipStream_t stream);
+// ---- sparse x dense and the dense / sparse conversions (gaamd_spmm.hip; ga_amd.h gaamd_spmm / _dense_row_counts /
+// _dense_to_csr / _csr_to_dense): the block CSR above, dense sides row-major with ld in elements; the codes are the
+// patch codes above (kPatchErrStride an ld below the stored row, kPatchErrOverlap an output on a dense input) ----
+int launch_spmm(int op, long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+                const void *val, const void *b, long long ldb, long long b_first, long long n, void *c, long long ldc,
+                hipStream_t stream);
+// store == false: counts[r] = the kept elements of row r; true: jdx / val at the prefix sums offs
+int launch_dense_csr(int op, long long rows, long long cols, const void *a, long long lda, long long row_first,
+                     long long col_first, int *counts, const int *offs, int *jdx, void *val, bool store,
+                     hipStream_t stream);
+int launch_csr_to_dense(int op, long long nrows, long long cols, const int *offs, const int *jdx, const void *val,
+                        long long col_first, void *out, long long ldo, hipStream_t stream);
 struct PatchPlan;
 // launch_patch_add's checks without a launch (no device): 0 launch, 1 nothing to do, < 0 error;
 // plan[0..3] = {vector width, row levels after merging, rows, vectors per row}

@@ -186,6 +186,29 @@ int gaamd_sprs_scale_right(int op, long long n, const int *jdx, void *val, const
     return launch_sprs_scale_right(op, n, jdx, val, d, d_first, stream_of(stream));
 }
 
+int gaamd_spmm(int op, long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+               const void *val, const void *b, long long ldb, long long b_first, long long n, void *c, long long ldc,
+               void *stream) {
+    return launch_spmm(op, nrows, nblk, offs, start, jdx, val, b, ldb, b_first, n, c, ldc, stream_of(stream));
+}
+
+int gaamd_dense_row_counts(int op, long long rows, long long cols, const void *a, long long lda, long long row_first,
+                           long long col_first, int *counts, void *stream) {
+    return launch_dense_csr(op, rows, cols, a, lda, row_first, col_first, counts, nullptr, nullptr, nullptr, false,
+                            stream_of(stream));
+}
+
+int gaamd_dense_to_csr(int op, long long rows, long long cols, const void *a, long long lda, long long row_first,
+                       long long col_first, const int *offs, int *jdx, void *val, void *stream) {
+    return launch_dense_csr(op, rows, cols, a, lda, row_first, col_first, nullptr, offs, jdx, val, true,
+                            stream_of(stream));
+}
+
+int gaamd_csr_to_dense(int op, long long nrows, long long cols, const int *offs, const int *jdx, const void *val,
+                       long long col_first, void *out, long long ldo, void *stream) {
+    return launch_csr_to_dense(op, nrows, cols, offs, jdx, val, col_first, out, ldo, stream_of(stream));
+}
+
 int gaamd_gemm(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
                const void *a, long long lda, const void *b, long long ldb, const void *beta, void *c, long long ldc,
                void *stream) {

@@ -393,8 +393,47 @@ void GA_Unpack(int g_src, int g_dst, int g_msk, int lo, int hi, int *icount);
    without a value; any computing call, access_col_block and col_block_list before assemble; a
    second assemble; a handle that is not live; a vector of the wrong rank, length or type, or in a
    host segment; g_a == g_v; a rank that would hold 2^31 entries or more; a missing shift, scale or
-   g_d.  Not provided: the *64 forms, matmat_multiply, sprsdns / dnssprs_multiply, get_block,
-   get_column, create_from_dense / _sparse, export, count_sketch. */
+   g_d.
+   Sparse x dense and the conversions (sparse.array.c:3222-3840), all collective:
+     g_c = NGA_Sprs_array_sprsdns_multiply(s_a, g_b)      a NEW array g_c = S B
+   g_b has rank 2, C dimensions jdim x n, the matrix's type, lives in HBM and may be under any block
+   map.  g_c is idim x n and the caller's to destroy (gaamd_ga_live_arrays() rises by exactly one).
+   It is created on the sparse array's row cuts: one block of full rows per rank that owns rows
+   (sparse.array.c:3669-3696), block k on rank k.  Where every rank owns rows that is
+   NGA_Sprs_array_row_distribution's set and every owner writes its rows in place; where idim <
+   nproc the array has fewer blocks than ranks, and a rank whose rows lie in another rank's block
+   writes them through HBM scratch and NGA_Put's path, complete at the owner before the closing
+   sync.  The rule is vec_part's: in place when the rank's own block covers the patch, scratch
+   otherwise.  B is needed over the rows of the rank's column span (first column of its first
+   non-empty column block to the last of its last) and all n columns: used in place where that
+   patch lies in the rank's own block of g_b, else fetched into HBM scratch with NGA_Get's path.
+   Where a side goes through scratch the product runs in panels of columns, so that a scratch side
+   never holds more than 2^28 bytes (one column at the least); the bits do not change.  A rank
+   without rows launches nothing and takes part in the syncs.  gaamd_ga_spmm_route_counts: {B in
+   place, B through scratch, C in place, C through scratch}, once per call, on this rank.
+   Arithmetic contract: gaamd_spmm's (ga_amd.h) -- c_ij starts from +0 and takes one product and
+   one add per entry, never fused, in the order of the row's ONE list over the column blocks; the
+   true complex product; integers wrap.  So for a matrix whose duplicates keep their relative
+   order the product is the same bits on any number of ranks and under any block map of g_b, and
+   for n = 1 it is the matvec of team 1.
+     s_b = NGA_Sprs_array_create_from_dense(g_a)          a NEW assembled sparse array
+   g_a: rank 2, any type, HBM, any block map; unchanged.  The result has g_a's dimensions and type
+   and holds the elements that are != 0 (so not -0.0, but a NaN; complex: either part) and every
+   element of the diagonal, zero or not (sparse.array.c:3234, 3263).  Each rank runs
+   gaamd_dense_row_counts and gaamd_dense_to_csr on its own block where it lies, copies the CSR of
+   the kept elements only to the host and hands them to the assembly above: the result is bit for
+   bit what create, add_element of the kept elements and assemble give.  It counts as an assemble
+   in the statistics too.
+     g_d = NGA_Sprs_array_create_from_sparse(s_a)         a NEW dense idim x jdim array
+   on the row cuts under g_c's rule, zeroed, then every non-empty column block scattered by
+   gaamd_csr_to_dense; of duplicates of one (i, j) the last in storage order (get_diag's rule).
+   The three abort through GA_Error on every rank before the first sync or launch: a handle that
+   is not live or not assembled; an array of rank other than 2; a type that differs; g_b with other
+   than jdim rows; an array in a host segment.  A rank that would keep 2^31 entries or more ends
+   create_from_dense on every rank, after the counting launch and before anything is stored.
+   Not provided: the *64 forms, matmat_multiply, dnssprs_multiply (it needs every rank to read the
+   other ranks' CSR blocks, i.e. get_block), get_block, get_column, export, count_sketch; assembly
+   still sorts on the host. */
 int NGA_Sprs_array_create(int idim, int jdim, int type);
 void NGA_Sprs_array_add_element(int s_a, int idx, int jdx, void *val);
 int NGA_Sprs_array_assemble(int s_a);
@@ -412,6 +451,10 @@ void NGA_Sprs_array_diag_left_multiply(int s_a, int g_d);
 void NGA_Sprs_array_diag_right_multiply(int s_a, int g_d);
 void gaamd_ga_sprs_range(long dim, int nproc, int iproc, long *lo, long *hi);
 void gaamd_ga_sprs_route_counts(long long counts[4]);
+int NGA_Sprs_array_sprsdns_multiply(int s_a, int g_b);
+int NGA_Sprs_array_create_from_dense(int g_a);
+int NGA_Sprs_array_create_from_sparse(int s_a);
+void gaamd_ga_spmm_route_counts(long long counts[4]);
 /* global arrays alive on this rank (temporaries of the general path are destroyed
    before their call returns) */
 int gaamd_ga_live_arrays(void);

@@ -340,6 +340,59 @@ int gaamd_sprs_diag(int op, int fn, long long nrows, const int *offs, const int 
 int gaamd_sprs_scale_left(int op, long long nrows, const int *offs, void *val, const void *d, int team, void *stream);
 int gaamd_sprs_scale_right(int op, long long n, const int *jdx, void *val, const void *d, long long d_first,
                            void *stream);
+/* Sparse x dense, and the conversions between a dense block and the block CSR; the kernels under
+ * NGA_Sprs_array_sprsdns_multiply, _create_from_dense and _create_from_sparse (ga.h).  All six
+ * types.  The dense sides are row-major with ld ELEMENTS between rows, all HBM.
+ *   gaamd_spmm   c[r][j] = sum over row r's list of val * b[jdx - b_first][j], r < nrows, j < n; the
+ *                block CSR is gaamd_spmv's; b[0] is global row b_first of B; c is nrows x n.
+ * Arithmetic and order (a contract): c[r][j] starts from +0 and takes, per entry, one product and
+ * then one add, never fused, the entries in the order of the row's ONE list over the column
+ * blocks ascending: acc = acc + val * b.  Integers wrap.  A complex product is the true product
+ * re = a.re*b.re - a.im*b.im, im = a.re*b.im + a.im*b.re, added part by part.  A row without
+ * entries gives +0; c is OVERWRITTEN.  Of b nothing is read but the rows the entries name; the gap
+ * ldc - n of c is not written.  Each (r, j) being one sequential sum, the bits do not depend on
+ * the grid, the tiling, the vector width or on how the list is cut into blocks; column 0 of an
+ * n = 1 product is gaamd_spmv with team 1, bit for bit.
+ * Shape: the lanes of a wave run along j; a row is taken by a group of G = 2^k lanes, each holding
+ * V consecutive columns, 256 / G rows per workgroup (so 64 / G rows per wave for narrow n).  V is
+ * 16 bytes' worth where b, c are 16-byte aligned and ldb, ldc, n are multiples of V, else 1.  G is
+ * the smallest power of two with G * V >= n, at most 64; wider n is cut into tiles of G * V
+ * columns over the grid's second dimension, the row's jdx / val being read once per tile.  The lanes
+ * of a group read val[k] / jdx[k] by the same-address load.  Rows: a 64-bit stride loop.
+ *   gaamd_dense_row_counts   counts[r] = the kept elements of row r of the rows x cols block a,
+ *                whose element (0, 0) is global (row_first, col_first).  KEPT: the value != 0 (so
+ *                -0.0 is not kept, a NaN is; complex: either part) or the element lies on the global
+ *                diagonal, row_first + r == col_first + c (sparse.array.c:3234, 3263).
+ *   gaamd_dense_to_csr   offs = the rows + 1 exclusive prefix sums of those counts (HBM): the kept
+ *                elements of row r go to jdx / val at offs[r] .., in ascending column order, jdx the
+ *                GLOBAL column col_first + c, val the bits unchanged.
+ *                Both walk a row in runs of 64 consecutive columns, one wave per row; a ballot and a
+ *                count of the lanes below give each kept lane its place.
+ *   gaamd_csr_to_dense   ONE column block (as gaamd_sprs_diag takes it) into the nrows x cols window
+ *                `out` whose column 0 is global column col_first: out[r][jdx - col_first] = val.
+ *                The caller zeroes `out`; nothing else of it is written.  Of duplicates of one (r, j),
+ *                which lie side by side, the last in storage order is stored: an entry whose successor
+ *                in the row names the same column is skipped, so no address has two writers.  An
+ *                entry outside the window is not stored.
+ * No atomics, no LDS, no scratch; every index into every array is 64-bit (k_spmm: 43 to 74 VGPRs).
+ * Negative codes, all before any launch, in this order: -3 a negative count (nrows, nblk, n, rows,
+ * cols); -4 an unknown op; then a zero nrows, n, rows or cols: 0 and no launch; -5 a missing
+ * pointer (gaamd_spmm with nblk == 0 needs c only); -6 an ld below the stored row length (ldb with
+ * nblk > 0, ldc, lda, ldo); -7 nrows or rows above 2^40, n or cols above 2^31 - 1, a negative
+ * row_first or col_first, col_first + cols above 2^31; -8 a, b, c, val or out below the element's
+ * alignment, start below 8, offs, counts or jdx below 4; -11 the byte span of the output (c;
+ * counts; jdx / val; out) overlaps that of a dense input or of offs.  Where a length is not an
+ * argument -- the rows of b the entries name, the offs[rows] entries of jdx / val -- the first
+ * row of b, the first entry of jdx / val stands for the span. */
+int gaamd_spmm(int op, long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+               const void *val, const void *b, long long ldb, long long b_first, long long n, void *c, long long ldc,
+               void *stream);
+int gaamd_dense_row_counts(int op, long long rows, long long cols, const void *a, long long lda, long long row_first,
+                           long long col_first, int *counts, void *stream);
+int gaamd_dense_to_csr(int op, long long rows, long long cols, const void *a, long long lda, long long row_first,
+                       long long col_first, const int *offs, int *jdx, void *val, void *stream);
+int gaamd_csr_to_dense(int op, long long nrows, long long cols, const int *offs, const int *jdx, const void *val,
+                       long long col_first, void *out, long long ldo, void *stream);
 /* Row-major GEMM on the gfx950 matrix cores, for op = COMEX_ACC_DBL (v_mfma_f64_16x16x4_f64)
  * and COMEX_ACC_FLT (v_mfma_f32_16x16x4_f32); the kernel under GA_Dgemm / GA_Sgemm (ga.h):
  *   C[i][j] = alpha * sum_k op(A)[i][k] * op(B)[k][j] + beta * C[i][j],  i < m, j < n, kk < k
