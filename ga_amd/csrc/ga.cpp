@@ -1572,24 +1572,117 @@ void NGA_Matmul_patch(char transa, char transb, void *alpha, void *beta, int g_a
 }
 int gaamd_ga_gemm_panel(void) { return (int)kGemmPanel; }
 
+// ---- a patch of another array as an operand of this rank's kernel ---------------------
+// The owner-computes calls below (transposes, matrix.c, pack / unpack, sparse arrays) each need
+// a patch of a 1-D or 2-D array that the caller's block map need not agree with.  A Part is
+// that patch for one kernel: the rank's own block in place where it holds the whole patch,
+// HBM scratch otherwise -- filled through NGA_Get's path for V_READ, stored back through
+// NGA_Put's path by part_done for V_WRITE.  Patches are internal (Fortran order, 1-based):
+// index 0 runs along a stored row.
+enum PartUse { V_NONE, V_READ, V_WRITE };
+enum PartPlace { P_AUTO, P_OWN, P_SCRATCH };   // P_AUTO: in place where own_holds() says so
+
+struct Part {
+    char *p = nullptr;
+    long long ld = 0;   // elements between stored rows (2-D): the block's in place, the patch's width in scratch
+    Scratch scratch;
+    int g = 0;          // what part_done stores back: the array, the patch and the use
+    long lo[2] = {0, 0}, hi[2] = {0, 0};
+    PartUse use = V_NONE;
+};
+
+// the 0-based inclusive ranges of the sparse code as a patch: index 0 (elements of a vector,
+// columns of a matrix), then index 1 (rows of a matrix)
+static Patch patch0(long long lo0, long long hi0, long long lo1 = 0, long long hi1 = 0) {
+    Patch p;
+    p.lo[0] = (long)lo0 + 1;
+    p.hi[0] = (long)hi0 + 1;
+    p.lo[1] = (long)lo1 + 1;
+    p.hi[1] = (long)hi1 + 1;
+    return p;
+}
+
+// this rank's own block holds the whole patch
+static bool own_holds(const GArray &a, const Patch &p) {
+    const Sub s = own_sub(a, p);
+    if (!s.any) return false;
+    for (int d = 0; d < a.ndim; d++)
+        if (s.count[d] != p.hi[d] - p.lo[d] + 1) return false;
+    return true;
+}
+
+// `cap` (1-D): the kernel may touch cap elements from p.lo[0] although only the patch holds data --
+// in place only where all of them stay inside the block, else scratch of cap elements.
+// `block`: the scratch is a whole block's mirror, and a failed allocation says so.
+static Part part(int g, const Patch &p, PartUse use, const char *what, PartPlace place = P_AUTO, long cap = 0,
+                 bool block = false) {
+    Part r;
+    GArray &a = arr(g);
+    r.g = g;
+    r.use = use;
+    for (int d = 0; d < a.ndim; d++) { r.lo[d] = p.lo[d]; r.hi[d] = p.hi[d]; }
+    if (place == P_AUTO) {
+        Patch room = p;
+        if (cap) room.hi[0] = p.lo[0] + cap - 1;
+        place = own_holds(a, room) ? P_OWN : P_SCRATCH;
+    }
+    if (place == P_OWN) {
+        const Sub s = own_sub(a, p);
+        r.p = s.p;
+        r.ld = a.ndim > 1 ? s.ext[0] : 0;
+        return r;
+    }
+    const long long n = cap ? cap : p.hi[0] - p.lo[0] + 1, rows = a.ndim > 1 ? p.hi[1] - p.lo[1] + 1 : 1;
+    r.ld = a.ndim > 1 ? n : 0;
+    r.p = (char *)r.scratch.alloc((size_t)rows * (size_t)n * a.elemsize);
+    if (!r.p) {
+        if (a.ndim == 1) fatal("%s: no device memory for %ld elements of scratch", what, (long)n);
+        fatal(block ? "%s: no device memory for the %lld x %lld scratch block"
+                    : "%s: no device memory for %lld x %lld elements of scratch", what, rows, n);
+    }
+    const long ld[1] = {(long)r.ld};
+    if (use == V_READ) patch_op(GA_GET, g, r.lo, r.hi, r.p, ld, nullptr);
+    return r;
+}
+
+// the kernel that used the part is waited for; scratch it has written is stored into the array
+// and complete at its owner; scratch is freed
+static void part_done(Part &r, const char *what) {
+    stream_wait(what);
+    if (!r.scratch.p) return;
+    if (r.use == V_WRITE) {
+        const long ld[1] = {(long)r.ld};
+        patch_op(GA_PUT, r.g, r.lo, r.hi, r.scratch.p, ld, nullptr);
+        comex_fence_all(COMEX_GROUP_WORLD);
+    }
+    r.scratch.free();
+}
+
+// a vector for a computing call: rank 1, `len` elements, of `type`, in HBM.  `of`: the name of the
+// dense array whose type that is, null for a sparse array
+static void need_vector(int g_v, int type, const char *of, long len, const char *what) {
+    const GArray &v = arr(g_v);
+    if (v.ndim != 1) fatal("%s: '%s' has rank %d, a vector of rank 1 is needed", what, v.name.c_str(), v.ndim);
+    if (v.type != type && of) fatal("%s: types of '%s' and '%s' differ", what, of, v.name.c_str());
+    if (v.type != type) fatal("%s: the type of '%s' differs from the sparse array's", what, v.name.c_str());
+    if (v.dims[0] != len) fatal("%s: '%s' has %ld elements, %ld are needed", what, v.name.c_str(), v.dims[0], len);
+    need_hbm(v, what);
+}
+
 // ---- GA_Transpose / GA_Symmetrize ----------------------------------------------------
 // pnga_transpose (global.nalg.c:954) transposes a rank's block of A in a host buffer and
 // puts it into B; pnga_symmetrize (ga_symmetr.c:49) gets the mirror of a rank's block into
 // a host buffer and adds it there.  Here the destination's owner computes, as matmul_patch
 // does: a rank takes its own block of the destination -- rows r0..r1, columns c0..c1 as
-// stored -- gets the mirror patch of the source (rows c0..c1, columns r0..r1) into HBM
-// scratch of one block's size with NGA_Get's path, and runs the LDS-tiled kernel from the
-// scratch into its block in place.  The block maps of source and destination need not agree.
+// stored -- takes the mirror patch of the source (rows c0..c1, columns r0..r1) as a Part, and
+// runs the LDS-tiled kernel from it into its block in place.  The block maps of source and
+// destination need not agree.
 
-// the mirror of this rank's part `s` of a 2-D array, fetched from g_src into new scratch:
-// stored count[0] x count[1] with ld = count[1]
-static Scratch get_mirror(int g_src, const GArray &dst, const Sub &s, const char *what) {
-    Scratch buf;
-    if (!buf.alloc((size_t)s.count[0] * (size_t)s.count[1] * dst.elemsize))
-        fatal("%s: no device memory for the %lld x %lld scratch block", what, s.count[0], s.count[1]);
-    const long lo[2] = {s.plo[1], s.plo[0]}, hi[2] = {s.phi[1], s.phi[0]}, ld[1] = {(long)s.count[1]};
-    patch_op(GA_GET, g_src, lo, hi, buf.p, ld, nullptr);
-    return buf;
+// the mirror of this rank's part `s` of a 2-D array: count[0] rows of count[1]
+static Patch mirror_of(const Sub &s) {
+    Patch m;
+    for (int d = 0; d < 2; d++) { m.lo[d] = s.plo[1 - d]; m.hi[d] = s.phi[1 - d]; }
+    return m;
 }
 
 void GA_Transpose(int g_a, int g_b) {
@@ -1609,17 +1702,9 @@ void GA_Transpose(int g_a, int g_b) {
     if (s.any) {
         // the block is count[1] rows of count[0]; its mirror in A is count[0] rows of count[1].
         // A mirror that lies wholly in this rank's own block of A is read there, without a get.
-        Patch mirror;
-        for (int d = 0; d < 2; d++) { mirror.lo[d] = s.plo[1 - d]; mirror.hi[d] = s.phi[1 - d]; }
-        const Sub sa = own_sub(a, mirror);
-        const bool own = sa.any && sa.count[0] == s.count[1] && sa.count[1] == s.count[0];
-        Scratch buf;
-        if (!own) buf = get_mirror(g_a, b, s, what);
-        launched(gaamd_transpose(b.optype, s.count[0], s.count[1], own ? sa.p : buf.p, own ? sa.ext[0] : s.count[1], s.p,
-                                 s.ext[0], gaamd_stream()),
-                 what);
-        stream_wait(what);
-        buf.free();
+        Part src = part(g_a, mirror_of(s), V_READ, what, P_AUTO, 0, true);
+        launched(gaamd_transpose(b.optype, s.count[0], s.count[1], src.p, src.ld, s.p, s.ext[0], gaamd_stream()), what);
+        part_done(src, what);
         g_stat.mathloc += 2 * s.bytes;
     }
     math_end(what);
@@ -1637,19 +1722,18 @@ void GA_Symmetrize(int g_a) {
     const Sub s = own_sub(a, Patch(a, nullptr, nullptr));
     // always through the scratch copy, on one rank too: in place, a block on the diagonal
     // would read what it is writing
-    Scratch buf;
-    if (s.any) buf = get_mirror(g_a, a, s, what);
+    Part buf;
+    if (s.any) buf = part(g_a, mirror_of(s), V_READ, what, P_SCRATCH, 0, true);
     stream_wait(what);
     comex_barrier(COMEX_GROUP_WORLD);   // every rank has read before any rank writes (ga_symmetr.c:105)
     if (s.any) {
         const double half_d = 0.5;
         const float half_f = 0.5f;
         const void *half = a.type == C_DBL ? (const void *)&half_d : (const void *)&half_f;
-        launched(gaamd_transpose_acc(a.optype, s.count[1], s.count[0], half, buf.p, s.count[1], s.p, s.ext[0],
+        launched(gaamd_transpose_acc(a.optype, s.count[1], s.count[0], half, buf.p, buf.ld, s.p, s.ext[0],
                                      gaamd_stream()),
                  what);
-        stream_wait(what);
-        buf.free();
+        part_done(buf, what);
         g_stat.mathloc += 3 * s.bytes;
     }
     math_end(what);
@@ -1657,60 +1741,16 @@ void GA_Symmetrize(int g_a) {
 
 // ---- diagonals, row / column scaling, norms (global/src/matrix.c) ------------------------
 // The reference fetches the part of g_v a rank's block needs into a host buffer and loops over
-// the block on the host.  Here the owner of g_a computes in HBM: the part of g_v is used in
-// place where it lies in the rank's own block of g_v, and goes through HBM scratch and
-// NGA_Get's / NGA_Put's path otherwise (as get_mirror does for the transposes).
+// the block on the host.  Here the owner of g_a computes in HBM, and the elements of g_v its
+// block needs are a Part (above).
 // Internally (Fortran order) index 0 runs along a stored row: C subscript j is index 0, C
 // subscript i is index 1; a block is count[1] rows of count[0] with ext[0] between rows.
-enum VecUse { V_NONE, V_READ, V_WRITE };
-
-// elements [lo, hi] (1-based) of the 1-D array g_v for this rank's kernel: its own block in
-// place, or scratch (filled by a get for V_READ)
-struct VecPart {
-    void *p = nullptr;
-    Scratch scratch;
-};
-static VecPart vec_part(int g_v, long lo, long hi, VecUse use, const char *what) {
-    VecPart r;
-    GArray &v = arr(g_v);
-    const Sub sv = own_sub(v, Patch(lo, hi));
-    if (sv.any && sv.count[0] == hi - lo + 1) {
-        r.p = sv.p;
-        return r;
-    }
-    r.p = r.scratch.alloc((size_t)(hi - lo + 1) * v.elemsize);
-    if (!r.p) fatal("%s: no device memory for %ld elements of scratch", what, hi - lo + 1);
-    const long ld[1] = {0};
-    if (use == V_READ) patch_op(GA_GET, g_v, &lo, &hi, r.p, ld, nullptr);
-    return r;
-}
-
-// the kernel has written the scratch: store it into g_v, complete at its owner, and free it
-static void vec_done(int g_v, long lo, long hi, VecPart &r, VecUse use, const char *what) {
-    stream_wait(what);
-    if (!r.scratch.p) return;
-    if (use == V_WRITE) {
-        const long ld[1] = {0};
-        patch_op(GA_PUT, g_v, &lo, &hi, r.scratch.p, ld, nullptr);
-        comex_fence_all(COMEX_GROUP_WORLD);
-    }
-    r.scratch.free();
-}
-
-static void need_vector(const GArray &a, int g_v, long len, const char *what) {
-    const GArray &v = arr(g_v);
-    if (v.ndim != 1) fatal("%s: '%s' has rank %d, a vector of rank 1 is needed", what, v.name.c_str(), v.ndim);
-    if (v.type != a.type) fatal("%s: types of '%s' and '%s' differ", what, a.name.c_str(), v.name.c_str());
-    if (v.dims[0] != len) fatal("%s: '%s' has %ld elements, %ld are needed", what, v.name.c_str(), v.dims[0], len);
-    need_hbm(v, what);
-}
-
 static void diagonal_call(int fn, int g_a, int g_v, const void *c, const char *what) {
     GArray &a = arr(g_a);
     if (a.ndim != 2) fatal("%s: arrays of rank other than 2 are not supported", what);
     need_hbm(a, what);
-    const VecUse use = fn == GAAMD_DIAG_GET ? V_WRITE : (fn == GAAMD_DIAG_SET || fn == GAAMD_DIAG_ADD) ? V_READ : V_NONE;
-    if (use != V_NONE) need_vector(a, g_v, std::min(a.dims[0], a.dims[1]), what);
+    const PartUse use = fn == GAAMD_DIAG_GET ? V_WRITE : (fn == GAAMD_DIAG_SET || fn == GAAMD_DIAG_ADD) ? V_READ : V_NONE;
+    if (use != V_NONE) need_vector(g_v, a.type, a.name.c_str(), std::min(a.dims[0], a.dims[1]), what);
     if (fn == GAAMD_DIAG_SHIFT && !c) fatal("%s: the constant is missing", what);
     comex_barrier(COMEX_GROUP_WORLD);
     g_stat.numdiag++;
@@ -1720,12 +1760,12 @@ static void diagonal_call(int fn, int g_a, int g_v, const void *c, const char *w
     if (d0 <= d1) {
         const long n = d1 - d0 + 1;
         char *p = s.p + ((d0 - s.plo[1]) * s.ext[0] + (d0 - s.plo[0])) * a.elemsize;
-        VecPart v;
-        if (use != V_NONE) v = vec_part(g_v, d0, d1, use, what);
+        Part v;
+        if (use != V_NONE) v = part(g_v, Patch(d0, d1), use, what);
         launched(gaamd_diagonal(a.optype, fn, n, p, (long long)(s.ext[0] + 1) * a.elemsize, v.p, a.elemsize, c,
                                 gaamd_stream()),
                  what);
-        vec_done(g_v, d0, d1, v, use, what);
+        part_done(v, what);
         g_stat.mathloc += (double)n * a.elemsize * (use == V_NONE && fn == GAAMD_DIAG_ZERO ? 1 : 2);
     }
     math_end(what);
@@ -1737,16 +1777,16 @@ static void scale_rc_call(bool rows, int g_a, int g_v, const char *what) {
     need_hbm(a, what);
     // C subscript i (rows) is internal index 1, j (columns) internal index 0
     const int dim = rows ? 1 : 0;
-    need_vector(a, g_v, a.dims[dim], what);
+    need_vector(g_v, a.type, a.name.c_str(), a.dims[dim], what);
     comex_barrier(COMEX_GROUP_WORLD);
     (rows ? g_stat.numscalerows : g_stat.numscalecols)++;
     const Sub s = own_sub(a, Patch(a, nullptr, nullptr));
     if (s.any) {
-        VecPart v = vec_part(g_v, s.plo[dim], s.phi[dim], V_READ, what);
+        Part v = part(g_v, Patch(s.plo[dim], s.phi[dim]), V_READ, what);
         launched(rows ? gaamd_scale_rows(a.optype, s.count[1], s.count[0], s.p, s.ext[0], v.p, gaamd_stream())
                       : gaamd_scale_cols(a.optype, s.count[1], s.count[0], s.p, s.ext[0], v.p, gaamd_stream()),
                  what);
-        vec_done(g_v, s.plo[dim], s.phi[dim], v, V_READ, what);
+        part_done(v, what);
         g_stat.mathloc += 2 * s.bytes;
     }
     math_end(what);
@@ -1896,24 +1936,6 @@ static void scan_call(int fn, int g_src, int g_dst, int g_msk, long lo, long hi,
     math_end(what);
 }
 
-// the packed side: elements [place + 1, place + cnt] (1-based) of g_b for this rank's kernel.
-// The kernel judges overlap with `packed` at n elements, so the rank's own block is used in
-// place only where n elements from there stay inside it; otherwise scratch of n elements.
-static VecPart packed_part(int g_b, long place, long cnt, long n, bool read, const char *what) {
-    VecPart r;
-    GArray &b = arr(g_b);
-    long lo = place + 1, hi = place + cnt, blo[GA_MAX_DIM], bhi[GA_MAX_DIM];
-    if (block_elems(b, my_rank(), blo, bhi) > 0 && blo[0] <= lo && lo + n - 1 <= bhi[0]) {
-        r.p = (char *)b.ptr[my_rank()] + (lo - blo[0]) * b.elemsize;
-        return r;
-    }
-    r.p = r.scratch.alloc((size_t)n * b.elemsize);
-    if (!r.p) fatal("%s: no device memory for %ld elements of scratch", what, n);
-    const long ld[1] = {0};
-    if (read) patch_op(GA_GET, g_b, &lo, &hi, r.p, ld, nullptr);
-    return r;
-}
-
 static void pack_call(bool unpack, int g_src, int g_dst, int g_msk, long lo, long hi, int *icount) {
     const char *what = unpack ? "GA_Unpack" : "GA_Pack";
     GArray &src = arr(g_src), &dst = arr(g_dst), &msk = arr(g_msk);
@@ -1951,11 +1973,13 @@ static void pack_call(bool unpack, int g_src, int g_dst, int g_msk, long lo, lon
     const long cnt = counts[(size_t)me];
     if (cnt > 0) {
         const long n = sm.count[0];
-        VecPart v = packed_part(g_thin, place, cnt, n, unpack, what);
+        // the packed side: cnt elements from `place` on.  The kernel judges overlap with it at n
+        // elements, so the part has room for n
+        Part v = part(g_thin, patch0(place, place + cnt - 1), unpack ? V_READ : V_WRITE, what, P_AUTO, n);
         launched(unpack ? gaamd_mask_unpack(full.optype, msk.optype, n, v.p, sm.p, sf.p, gaamd_stream())
                         : gaamd_mask_pack(full.optype, msk.optype, n, sf.p, sm.p, v.p, gaamd_stream()),
                  what);
-        vec_done(g_thin, place + 1, place + cnt, v, unpack ? V_READ : V_WRITE, what);
+        part_done(v, what);
         g_stat.mathloc += 3.0 * sm.bytes + 2.0 * cnt * full.elemsize;   // msk three times, cnt elements in and out
     }
     math_end(what);
@@ -1982,8 +2006,8 @@ void GA_Unpack(int g_src, int g_dst, int g_msk, int lo, int hi, int *icount) {
 // element to the owner of its row (a table of counts through exchange_slots, then one comex_put
 // per owner into a segment of the incoming size), and the owner sorts on the host
 // (sprs_build.hpp) and uploads the block CSR into plain HBM allocations once.  The computing
-// calls run the kernels of ga_amd.h on that CSR where it lies; the vectors come through
-// vec_part / vec_done as in the matrix.c calls.
+// calls run the kernels of ga_amd.h on that CSR where it lies; the vectors are Parts, as in
+// the matrix.c calls.
 enum SprsCall { SP_ASSEMBLE, SP_MATVEC, SP_GET_DIAG, SP_SHIFT_DIAG, SP_SCALE, SP_DIAG_LEFT, SP_DIAG_RIGHT };
 
 struct SprsArray {
@@ -2048,15 +2072,6 @@ static void sprs_release_all() {
 static const int *sprs_offs(const SprsArray &s, size_t b) { return s.offs + b * (size_t)(s.nrows + 1); }
 static char *sprs_val(const SprsArray &s, size_t b) { return s.val + s.start[b] * s.elemsize; }
 
-// a vector for a computing call: rank 1, `len` elements, the matrix's type, in HBM
-static void need_sprs_vector(const SprsArray &s, int g_v, long len, const char *what) {
-    const GArray &v = arr(g_v);
-    if (v.ndim != 1) fatal("%s: '%s' has rank %d, a vector of rank 1 is needed", what, v.name.c_str(), v.ndim);
-    if (v.type != s.type) fatal("%s: the type of '%s' differs from the sparse array's", what, v.name.c_str());
-    if (v.dims[0] != len) fatal("%s: '%s' has %ld elements, %ld are needed", what, v.name.c_str(), v.dims[0], len);
-    need_hbm(v, what);
-}
-
 // the columns this rank's entries can name: first column of its first non-empty block to the
 // last column of its last one (0-based, inclusive); false when it has no entry
 static bool sprs_col_span(const SprsArray &s, long long *lo, long long *hi) {
@@ -2070,25 +2085,25 @@ static bool sprs_col_span(const SprsArray &s, long long *lo, long long *hi) {
 static void sprs_matvec(int s_a, int g_a, int g_v) {
     const char *what = "NGA_Sprs_array_matvec_multiply";
     SprsArray &s = sprs_assembled(s_a, what);
-    need_sprs_vector(s, g_a, s.jdim, what);
-    need_sprs_vector(s, g_v, s.idim, what);
+    need_vector(g_a, s.type, nullptr, s.jdim, what);
+    need_vector(g_v, s.type, nullptr, s.idim, what);
     if (g_a == g_v) fatal("%s: the vector and the product must be different arrays", what);
     comex_barrier(COMEX_GROUP_WORLD);
     g_stat.numsprs[SP_MATVEC]++;
     if (s.nrows > 0) {
         long long c0 = 0, c1 = -1;
-        VecPart x;
+        Part x;
         if (sprs_col_span(s, &c0, &c1)) {
-            x = vec_part(g_a, (long)c0 + 1, (long)c1 + 1, V_READ, what);
+            x = part(g_a, patch0(c0, c1), V_READ, what);
             g_sprs_routes[x.scratch.p ? 1 : 0]++;
         }
-        VecPart y = vec_part(g_v, (long)s.ilo + 1, (long)(s.ilo + s.nrows), V_WRITE, what);
+        Part y = part(g_v, patch0(s.ilo, s.ilo + s.nrows - 1), V_WRITE, what);
         g_sprs_routes[y.scratch.p ? 3 : 2]++;
         launched(gaamd_spmv(s.optype, s.nrows, (int)s.blocks.size(), s.offs, s.dstart, s.jdx, s.val, x.p, c0, y.p, s.team,
                             gaamd_stream()),
                  what);
-        vec_done(g_a, (long)c0 + 1, (long)c1 + 1, x, V_READ, what);
-        vec_done(g_v, (long)s.ilo + 1, (long)(s.ilo + s.nrows), y, V_WRITE, what);
+        part_done(x, what);
+        part_done(y, what);
         g_stat.mathloc += (double)s.nnz * (2.0 * s.elemsize + 4) + (double)s.nrows * s.elemsize;
     }
     math_end(what);
@@ -2098,12 +2113,12 @@ static void sprs_matvec(int s_a, int g_a, int g_v) {
 static void sprs_diag_multiply(bool left, int s_a, int g_d) {
     const char *what = left ? "NGA_Sprs_array_diag_left_multiply" : "NGA_Sprs_array_diag_right_multiply";
     SprsArray &s = sprs_assembled(s_a, what);
-    need_sprs_vector(s, g_d, left ? s.idim : s.jdim, what);
+    need_vector(g_d, s.type, nullptr, left ? s.idim : s.jdim, what);
     comex_barrier(COMEX_GROUP_WORLD);
     g_stat.numsprs[left ? SP_DIAG_LEFT : SP_DIAG_RIGHT]++;
     long long lo = s.ilo, hi = s.ilo + s.nrows - 1;
     if (s.nnz > 0 && (left || sprs_col_span(s, &lo, &hi))) {
-        VecPart d = vec_part(g_d, (long)lo + 1, (long)hi + 1, V_READ, what);
+        Part d = part(g_d, patch0(lo, hi), V_READ, what);
         if (left) {
             for (size_t b = 0; b < s.blocks.size(); b++)
                 launched(gaamd_sprs_scale_left(s.optype, s.nrows, sprs_offs(s, b), sprs_val(s, b), d.p, s.team,
@@ -2112,7 +2127,7 @@ static void sprs_diag_multiply(bool left, int s_a, int g_d) {
         } else {
             launched(gaamd_sprs_scale_right(s.optype, s.nnz, s.jdx, s.val, d.p, lo, gaamd_stream()), what);
         }
-        vec_done(g_d, (long)lo + 1, (long)hi + 1, d, V_READ, what);
+        part_done(d, what);
         g_stat.mathloc += (double)s.nnz * (3.0 * s.elemsize + (left ? 0 : 4));
     }
     math_end(what);
@@ -2393,56 +2408,11 @@ static GArray sprs_row_array(const SprsArray &s, long ncols, const char *name) {
     return d;
 }
 
-// rows [r0, r1] x columns [j0, j1] (0-based, inclusive) of the 2-D array g for this rank's kernel: in
-// place (ld the block's) where the rank's own block covers rows [r0, r1] x ALL columns, else scratch
-// of the panel (ld its width), filled by a get for V_READ
-struct MatPart {
-    char *p = nullptr;
-    long long ld = 0;
-    Scratch scratch;
-};
-static bool mat_in_place(int g, long long r0, long long r1) {
+// this rank's own block of the 2-D array g holds rows [r0, r1] (0-based) at ALL columns: panels of those
+// rows are used in place.  Asked once per call, so every panel goes the same way
+static bool own_holds_rows(int g, long long r0, long long r1) {
     const GArray &a = arr(g);
-    Patch p;
-    p.lo[0] = 1;
-    p.hi[0] = a.dims[0];
-    p.lo[1] = (long)r0 + 1;
-    p.hi[1] = (long)r1 + 1;
-    const Sub s = own_sub(a, p);
-    return s.any && s.count[0] == a.dims[0] && s.count[1] == r1 - r0 + 1;
-}
-static MatPart mat_part(int g, bool in_place, long long r0, long long r1, long long j0, long long j1, VecUse use,
-                        const char *what) {
-    MatPart r;
-    GArray &a = arr(g);
-    Patch p;
-    p.lo[0] = (long)j0 + 1;
-    p.hi[0] = (long)j1 + 1;
-    p.lo[1] = (long)r0 + 1;
-    p.hi[1] = (long)r1 + 1;
-    if (in_place) {
-        const Sub s = own_sub(a, p);
-        r.p = s.p;
-        r.ld = s.ext[0];
-        return r;
-    }
-    r.ld = j1 - j0 + 1;
-    r.p = (char *)r.scratch.alloc((size_t)(r1 - r0 + 1) * (size_t)r.ld * a.elemsize);
-    if (!r.p) fatal("%s: no device memory for %lld x %lld elements of scratch", what, r1 - r0 + 1, r.ld);
-    const long ld[1] = {(long)r.ld};
-    if (use == V_READ) patch_op(GA_GET, g, p.lo, p.hi, r.p, ld, nullptr);
-    return r;
-}
-// the kernel has written the scratch: store it, complete at its owner, and free it
-static void mat_done(int g, long long r0, long long r1, long long j0, long long j1, MatPart &r, VecUse use, const char *what) {
-    stream_wait(what);
-    if (!r.scratch.p) return;
-    if (use == V_WRITE) {
-        const long lo[2] = {(long)j0 + 1, (long)r0 + 1}, hi[2] = {(long)j1 + 1, (long)r1 + 1}, ld[1] = {(long)r.ld};
-        patch_op(GA_PUT, g, lo, hi, r.scratch.p, ld, nullptr);
-        comex_fence_all(COMEX_GROUP_WORLD);
-    }
-    r.scratch.free();
+    return own_holds(a, patch0(0, a.dims[0] - 1, r0, r1));
 }
 
 int NGA_Sprs_array_sprsdns_multiply(int s_a, int g_b) {
@@ -2466,7 +2436,7 @@ int NGA_Sprs_array_sprsdns_multiply(int s_a, int g_b) {
         const long long r0 = s.ilo, r1 = s.ilo + s.nrows - 1;
         long long c0 = 0, c1 = -1;
         const bool has_b = sprs_col_span(s, &c0, &c1);
-        const bool b_own = has_b && mat_in_place(g_b, c0, c1), c_own = mat_in_place(g_c, r0, r1);
+        const bool b_own = has_b && own_holds_rows(g_b, c0, c1), c_own = own_holds_rows(g_c, r0, r1);
         if (has_b) g_spmm_routes[b_own ? 0 : 1]++;
         g_spmm_routes[c_own ? 2 : 3]++;
         // panels of columns bound each scratch side by kSpmmPanelBytes (one column at the least)
@@ -2477,14 +2447,14 @@ int NGA_Sprs_array_sprsdns_multiply(int s_a, int g_b) {
         if (rows_max > 0) pw = std::max<long long>(1, std::min<long long>(n, (long long)(kSpmmPanelBytes / s.elemsize) / rows_max));
         for (long long j0 = 0; j0 < n; j0 += pw) {
             const long long j1 = std::min<long long>(n, j0 + pw) - 1;
-            MatPart bp;
-            if (has_b) bp = mat_part(g_b, b_own, c0, c1, j0, j1, V_READ, what);
-            MatPart cp = mat_part(g_c, c_own, r0, r1, j0, j1, V_WRITE, what);
+            Part bp;
+            if (has_b) bp = part(g_b, patch0(j0, j1, c0, c1), V_READ, what, b_own ? P_OWN : P_SCRATCH);
+            Part cp = part(g_c, patch0(j0, j1, r0, r1), V_WRITE, what, c_own ? P_OWN : P_SCRATCH);
             launched(gaamd_spmm(s.optype, s.nrows, (int)s.blocks.size(), s.offs, s.dstart, s.jdx, s.val, bp.p, bp.ld, c0,
                                 j1 - j0 + 1, cp.p, cp.ld, gaamd_stream()),
                      what);
-            mat_done(g_c, r0, r1, j0, j1, cp, V_WRITE, what);
-            mat_done(g_b, c0, c1, j0, j1, bp, V_READ, what);
+            part_done(cp, what);
+            part_done(bp, what);
         }
         g_stat.mathloc += (double)s.nnz * (s.elemsize + 4) + ((double)s.nnz + (double)s.nrows) * (double)n * s.elemsize;
     }
@@ -2575,19 +2545,19 @@ int NGA_Sprs_array_create_from_sparse(int s_a) {
     g_spmm_calls[SM_FROM_SPARSE]++;
     if (s.nrows > 0 && s.nnz > 0) {
         const long long r0 = s.ilo, r1 = s.ilo + s.nrows - 1;
-        const bool own = mat_in_place(g_d, r0, r1);
+        const bool own = own_holds_rows(g_d, r0, r1);
         // rows that lie in another rank's block: full-width panels of rows, zeroed, scattered and put
         const long long rows_max = own ? s.nrows : std::max<long long>(1, (long long)(kSpmmPanelBytes / s.elemsize) / s.jdim);
         for (long long q0 = 0; q0 < s.nrows; q0 += rows_max) {
             const long long q1 = std::min<long long>(s.nrows, q0 + rows_max) - 1;
-            MatPart out = mat_part(g_d, own, r0 + q0, r0 + q1, 0, s.jdim - 1, V_WRITE, what);
+            Part out = part(g_d, patch0(0, s.jdim - 1, r0 + q0, r0 + q1), V_WRITE, what, own ? P_OWN : P_SCRATCH);
             if (!own && gaamd_memset(out.p, 0, (size_t)(q1 - q0 + 1) * (size_t)s.jdim * s.elemsize) != 0)
                 fatal("%s: zeroing the scratch failed", what);
             for (size_t b = 0; b < s.blocks.size(); b++)
                 launched(gaamd_csr_to_dense(s.optype, q1 - q0 + 1, s.jdim, sprs_offs(s, b) + q0, s.jdx + s.start[b],
                                             sprs_val(s, b), 0, out.p, out.ld, gaamd_stream()),
                          what);
-            mat_done(g_d, r0 + q0, r0 + q1, 0, s.jdim - 1, out, V_WRITE, what);
+            part_done(out, what);
         }
         g_stat.mathloc += (double)s.nnz * (2.0 * s.elemsize + 4);
     }

@@ -36,7 +36,7 @@ import test_gpu_ga_elem as E
 import test_gpu_ga_math as K
 import test_gpu_matrix as M
 import test_gpu_scan as S
-from ga_math_worker import C_DBL, C_DCPL, C_FLOAT, C_INT, C_LONG, C_SCPL, OP_OF, flat, sl
+from ga_worker import C_DBL, C_DCPL, C_FLOAT, C_INT, C_LONG, C_SCPL, OP_OF, flat, sl
 
 TYPES = [C_INT, C_LONG, C_FLOAT, C_DBL, C_SCPL, C_DCPL]
 KINDS = ["regular", "chunk", "irreg"]
@@ -796,7 +796,7 @@ def transposes(c, size):
 
 
 def vec_parts(c, size):
-    """{"in place", "scratch"} over the ranks: vec_part of the matrix calls, packed_part of pack / unpack"""
+    """{"in place", "scratch"} over the ranks: the Part of the matrix calls and of pack / unpack (room for n)"""
     call, g = c["call"], c["args"]
     out = set()
     if c["fam"] == "matrix" and "v" in g:

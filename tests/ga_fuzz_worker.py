@@ -32,7 +32,7 @@ import numpy as np  # noqa: E402
 
 import ga_amd  # noqa: E402
 import ga_fuzz_cases as F  # noqa: E402
-from ga_math_worker import DOT_OF, C_DBL, blocks_of, ia, sl, vp  # noqa: E402
+from ga_worker import DOT_OF, C_DBL, blocks_of, ia, sl, vp  # noqa: E402
 
 SEED = int(os.environ.get("GAAMD_FUZZ_SEED", "0"))
 

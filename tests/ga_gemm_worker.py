@@ -24,6 +24,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 import ga_amd  # noqa: E402
+from ga_worker import run  # noqa: E402
 
 ia = ga_amd.int_array
 C_FLOAT, C_DBL = 1003, 1004
@@ -190,23 +191,5 @@ def bits(L, rank, size):
                 x.destroy()
 
 
-def main():
-    import faulthandler
-    faulthandler.dump_traceback_later(int(os.environ.get("TEST_STACK_DUMP_S", "600")), exit=False)
-    rank, size = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    L = ga_amd.lib()
-    assert L.GA_Initialize() == 0
-    live0 = L.gaamd_ga_live_arrays()
-    for name, fn in (("exact", exact), ("maps", maps), ("bits", bits)):
-        fn(L, rank, size)
-        L.GA_Sync()
-        assert L.gaamd_ga_live_arrays() == live0, "a call left a global array alive"
-        print(f"SECTION {name} OK", flush=True)
-    sys.stdout.flush()
-    L.GA_Print_stats()
-    L.GA_Terminate()
-    print(f"RANK {rank} OK", flush=True)
-
-
 if __name__ == "__main__":
-    main()
+    run([("exact", exact), ("maps", maps), ("bits", bits)], check_live=True)

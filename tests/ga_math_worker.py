@@ -28,64 +28,8 @@ import numpy as np  # noqa: E402
 import ga_amd  # noqa: E402
 import test_gpu_ga_math as K  # noqa: E402
 
-ia = ga_amd.int_array
-C_INT, C_LONG, C_FLOAT, C_DBL, C_SCPL, C_DCPL = 1001, 1002, 1003, 1004, 1006, 1007
-OP_OF = {C_INT: K.INT, C_LONG: K.LNG, C_FLOAT: K.FLT, C_DBL: K.DBL, C_SCPL: K.CPL, C_DCPL: K.DCP}
-DOT_OF = {C_INT: "I", C_LONG: "L", C_FLOAT: "F", C_DBL: "D", C_SCPL: "C", C_DCPL: "Z"}
-
-
-def vp(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
-class GA:
-    """a global array and its numpy model (C order)"""
-
-    def __init__(self, L, t, dims, name, irreg=None):
-        self.L, self.t, self.dims, self.op = L, t, list(dims), OP_OF[t]
-        self.dt = K.DT[self.op]
-        if irreg:
-            block, amap = irreg
-            self.g = L.NGA_Create_irreg(t, len(dims), ia(dims), name, ia(block), ia(amap))
-        else:
-            self.g = L.NGA_Create(t, len(dims), ia(dims), name, None)
-        assert self.g > 0
-        self.model = np.zeros(dims, dtype=self.dt)
-
-    def lohi(self):
-        return ia([0] * len(self.dims)), ia([d - 1 for d in self.dims])
-
-    def put(self, vals, rank):
-        """rank 0 writes the whole array; everyone syncs"""
-        vals = np.ascontiguousarray(vals.reshape(self.dims), dtype=self.dt)
-        self.L.GA_Sync()   # no rank still reads the old values
-        if rank == 0:
-            lo, hi = self.lohi()
-            self.L.NGA_Put(self.g, lo, hi, vp(vals), ia(self.dims[1:]))
-        self.L.GA_Sync()
-        self.model = vals.copy()
-
-    def get(self):
-        out = np.empty(self.dims, dtype=self.dt)
-        lo, hi = self.lohi()
-        self.L.NGA_Get(self.g, lo, hi, vp(out), ia(self.dims[1:]))
-        return out
-
-    def check(self, what):
-        got = self.get()
-        assert got.tobytes() == self.model.tobytes(), \
-            f"{what}: {np.count_nonzero(got != self.model)} of {got.size} elements differ"
-
-    def destroy(self):
-        self.L.GA_Destroy(self.g)
-
-
-def sl(lo, hi):
-    return tuple(slice(a, b + 1) for a, b in zip(lo, hi))
-
-
-def flat(x):
-    return np.ascontiguousarray(x).reshape(-1)
+from ga_worker import (C_DBL, C_DCPL, C_FLOAT, C_INT, C_LONG, C_SCPL, DOT_OF, GA, OP_OF, blocks_of, flat, ia, run,  # noqa: E402
+                       sl, vp)
 
 
 def dot_call(L, t, ga, gb, patch=None):
@@ -147,15 +91,6 @@ def whole_array(L, rank, size):
             say_dot(f"whole-{ga_amd.OP_NAME[op]}-{len(dims)}d", dot_call(L, t, a.g, b.g))
             for x in (a, b, c):
                 x.destroy()
-
-
-def blocks_of(L, g, nd, size):
-    out = []
-    for q in range(size):
-        lo, hi = (ctypes.c_int * nd)(), (ctypes.c_int * nd)()
-        L.NGA_Distribution(g, q, lo, hi)
-        out.append((list(lo), list(hi)))
-    return out
 
 
 def patch_forms(L, rank, size):
@@ -386,30 +321,6 @@ def aborts(L, rank, size, mode):
     print("NOT REACHED", flush=True)
 
 
-def main():
-    import faulthandler
-    faulthandler.dump_traceback_later(int(os.environ.get("TEST_STACK_DUMP_S", "600")), exit=False)
-    mode = sys.argv[1]
-    rank, size = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    L = ga_amd.lib()
-    assert L.GA_Initialize() == 0
-    if mode.startswith("abort"):
-        aborts(L, rank, size, mode)
-        sys.exit(3)
-    if mode == "big":
-        big(L, rank, size)
-    elif mode == "tall":
-        tall(L, rank, size)
-    else:
-        for name, fn in (("whole", whole_array), ("patch", patch_forms), ("general", general_path),
-                         ("order", ordering)):
-            fn(L, rank, size)
-            L.GA_Sync()
-            print(f"SECTION {name} OK", flush=True)
-        L.GA_Print_stats()
-    L.GA_Terminate()
-    print(f"RANK {rank} OK", flush=True)
-
-
 if __name__ == "__main__":
-    main()
+    run([("whole", whole_array), ("patch", patch_forms), ("general", general_path), ("order", ordering)], aborts,
+        bare={"big": big, "tall": tall})

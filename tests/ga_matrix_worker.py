@@ -25,7 +25,7 @@ import numpy as np  # noqa: E402
 import ga_amd  # noqa: E402
 import test_gpu_ga_math as K  # noqa: E402
 import test_gpu_matrix as M  # noqa: E402
-from ga_math_worker import C_DBL, C_DCPL, C_FLOAT, C_INT, C_LONG, C_SCPL, GA, blocks_of, vp  # noqa: E402
+from ga_worker import C_DBL, C_DCPL, C_FLOAT, C_INT, C_LONG, C_SCPL, GA, blocks_of, run, vp  # noqa: E402
 
 TYPES = (C_DBL, C_FLOAT, C_INT, C_LONG, C_DCPL)   # one complex type for the scale and diagonal calls
 NORM_TYPES = (C_DBL, C_FLOAT, C_INT, C_LONG, C_DCPL, C_SCPL)   # C_SCPL: norm_call's armci_msg_fgop branch
@@ -204,24 +204,5 @@ def aborts(L, rank, size, mode):
     print("NOT REACHED", flush=True)
 
 
-def main():
-    import faulthandler
-    faulthandler.dump_traceback_later(int(os.environ.get("TEST_STACK_DUMP_S", "600")), exit=False)
-    mode = sys.argv[1]
-    rank, size = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    L = ga_amd.lib()
-    assert L.GA_Initialize() == 0
-    if mode.startswith("abort"):
-        aborts(L, rank, size, mode)
-        sys.exit(3)
-    for name, fn in (("forms", forms), ("corners", corners), ("norms", norms)):
-        fn(L, rank, size)
-        L.GA_Sync()
-        print(f"SECTION {name} OK", flush=True)
-    L.GA_Print_stats()
-    L.GA_Terminate()
-    print(f"RANK {rank} OK", flush=True)
-
-
 if __name__ == "__main__":
-    main()
+    run([("forms", forms), ("corners", corners), ("norms", norms)], aborts)

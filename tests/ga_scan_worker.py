@@ -27,7 +27,7 @@ import numpy as np  # noqa: E402
 import ga_amd  # noqa: E402
 import test_gpu_ga_math as K  # noqa: E402
 import test_gpu_scan as S  # noqa: E402
-from ga_math_worker import C_DBL, C_DCPL, C_FLOAT, C_INT, C_LONG, C_SCPL, GA, OP_OF, blocks_of, vp  # noqa: E402
+from ga_worker import C_DBL, C_DCPL, C_FLOAT, C_INT, C_LONG, C_SCPL, GA, OP_OF, blocks_of, run, vp  # noqa: E402
 
 NELEM = 3001
 VALUE_TYPES = (C_INT, C_LONG, C_FLOAT, C_DBL, C_DCPL)
@@ -274,24 +274,5 @@ def aborts(L, rank, size, mode):
     print("NOT REACHED", flush=True)
 
 
-def main():
-    import faulthandler
-    faulthandler.dump_traceback_later(int(os.environ.get("TEST_STACK_DUMP_S", "600")), exit=False)
-    mode = sys.argv[1]
-    rank, size = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    L = ga_amd.lib()
-    assert L.GA_Initialize() == 0
-    if mode.startswith("abort"):
-        aborts(L, rank, size, mode)
-        sys.exit(3)
-    for name, fn in (("enums", enums), ("scans", scans), ("packs", packs), ("corners", corners)):
-        fn(L, rank, size)
-        L.GA_Sync()
-        print(f"SECTION {name} OK", flush=True)
-    L.GA_Print_stats()
-    L.GA_Terminate()
-    print(f"RANK {rank} OK", flush=True)
-
-
 if __name__ == "__main__":
-    main()
+    run([("enums", enums), ("scans", scans), ("packs", packs), ("corners", corners)], aborts)

@@ -33,7 +33,7 @@ import ga_sprs_worker as W  # noqa: E402
 import test_gpu_ga_math as K  # noqa: E402
 import test_gpu_spmm as M  # noqa: E402
 import test_gpu_sprs as S  # noqa: E402
-from ga_math_worker import C_DBL, C_LONG, C_SCPL, OP_OF, vp  # noqa: E402
+from ga_worker import C_DBL, C_LONG, C_SCPL, OP_OF, run, vp  # noqa: E402
 
 ia = ga_amd.int_array
 TYPES = (C_DBL, C_SCPL, C_LONG)
@@ -362,24 +362,5 @@ def aborts(L, rank, size, mode):
     print("NOT REACHED", flush=True)
 
 
-def main():
-    import faulthandler
-    faulthandler.dump_traceback_later(int(os.environ.get("TEST_STACK_DUMP_S", "600")), exit=False)
-    mode = sys.argv[1]
-    rank, size = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    L = ga_amd.lib()
-    assert L.GA_Initialize() == 0
-    if mode.startswith("abort"):
-        aborts(L, rank, size, mode)
-        sys.exit(3)
-    for name, fn in ((("four", four),) if mode == "four" else (("products", products), ("conversions", conversions))):
-        fn(L, rank, size)
-        L.GA_Sync()
-        print(f"SECTION {name} OK", flush=True)
-    L.GA_Print_stats()
-    L.GA_Terminate()
-    print(f"RANK {rank} OK", flush=True)
-
-
 if __name__ == "__main__":
-    main()
+    run({"all": [("products", products), ("conversions", conversions)], "four": [("four", four)]}, aborts)

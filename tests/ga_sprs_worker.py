@@ -31,7 +31,7 @@ import numpy as np  # noqa: E402
 import ga_amd  # noqa: E402
 import test_gpu_ga_math as K  # noqa: E402
 import test_gpu_sprs as S  # noqa: E402
-from ga_math_worker import C_DBL, C_DCPL, C_FLOAT, C_INT, C_LONG, C_SCPL, OP_OF, vp  # noqa: E402
+from ga_worker import C_DBL, C_DCPL, C_FLOAT, C_INT, C_LONG, C_SCPL, OP_OF, run, vp  # noqa: E402
 
 ia = ga_amd.int_array
 ALL_CALLS = (C_INT, C_LONG, C_FLOAT, C_DBL, C_DCPL)
@@ -315,24 +315,5 @@ def aborts(L, rank, size, mode):
     print("NOT REACHED", flush=True)
 
 
-def main():
-    import faulthandler
-    faulthandler.dump_traceback_later(int(os.environ.get("TEST_STACK_DUMP_S", "600")), exit=False)
-    mode = sys.argv[1]
-    rank, size = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    L = ga_amd.lib()
-    assert L.GA_Initialize() == 0
-    if mode.startswith("abort"):
-        aborts(L, rank, size, mode)
-        sys.exit(3)
-    for name, fn in (("products", products), ("others", others)):
-        fn(L, rank, size)
-        L.GA_Sync()
-        print(f"SECTION {name} OK", flush=True)
-    L.GA_Print_stats()
-    L.GA_Terminate()
-    print(f"RANK {rank} OK", flush=True)
-
-
 if __name__ == "__main__":
-    main()
+    run([("products", products), ("others", others)], aborts)

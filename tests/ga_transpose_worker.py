@@ -30,6 +30,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 import ga_amd  # noqa: E402
+from ga_worker import run  # noqa: E402
 
 ia = ga_amd.int_array
 C_INT, C_FLOAT, C_DBL, C_DCPL = 1001, 1003, 1004, 1007
@@ -221,27 +222,5 @@ def aborts(L, rank, size, mode):
     print("NOT REACHED", flush=True)
 
 
-def main():
-    import faulthandler
-    faulthandler.dump_traceback_later(int(os.environ.get("TEST_STACK_DUMP_S", "600")), exit=False)
-    mode = sys.argv[1] if len(sys.argv) > 1 else "all"
-    rank, size = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    L = ga_amd.lib()
-    assert L.GA_Initialize() == 0
-    if mode.startswith("abort"):
-        aborts(L, rank, size, mode)
-        sys.exit(3)
-    live0 = L.gaamd_ga_live_arrays()
-    for name, fn in (("transpose", transpose), ("maps", maps), ("symm", symm), ("bits", bits)):
-        fn(L, rank, size)
-        L.GA_Sync()
-        assert L.gaamd_ga_live_arrays() == live0, "a call left a global array alive"
-        print(f"SECTION {name} OK", flush=True)
-    sys.stdout.flush()
-    L.GA_Print_stats()
-    L.GA_Terminate()
-    print(f"RANK {rank} OK", flush=True)
-
-
 if __name__ == "__main__":
-    main()
+    run([("transpose", transpose), ("maps", maps), ("symm", symm), ("bits", bits)], aborts, check_live=True)

@@ -18,16 +18,14 @@ prints "ABORT EXPECTED" just before the call and "NOT REACHED" if it returns.
 """
 import ctypes
 import hashlib
-import os
-import sys
 
 import numpy as np
 
 import ga_gemm_worker as W   # the real worker's GA model and helpers (tests/ is sys.path[0])
 from ga_gemm_worker import GA, cuts, ia, stored_dims, vp
 
-import ga_amd  # noqa: E402  (ga_gemm_worker put the repository root on sys.path)
-from ga_amd._lib import DoubleComplex, SingleComplex  # noqa: E402
+from ga_amd._lib import DoubleComplex, SingleComplex  # noqa: E402  (ga_gemm_worker put the repository root on sys.path)
+from ga_worker import run  # noqa: E402
 
 C_DBL, C_SCPL, C_DCPL = 1004, 1006, 1007
 W.DT[C_SCPL] = np.dtype(np.complex64)      # GA() looks its element type up there
@@ -171,27 +169,5 @@ def aborts(L, rank, size, mode):
     print("NOT REACHED", flush=True)
 
 
-def main():
-    import faulthandler
-    faulthandler.dump_traceback_later(int(os.environ.get("TEST_STACK_DUMP_S", "600")), exit=False)
-    mode = sys.argv[1] if len(sys.argv) > 1 else "all"
-    rank, size = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    L = ga_amd.lib()
-    assert L.GA_Initialize() == 0
-    if mode.startswith("abort"):
-        aborts(L, rank, size, mode)
-        sys.exit(3)
-    live0 = L.gaamd_ga_live_arrays()
-    for name, fn in (("exact", exact), ("maps", maps), ("bits", bits)):
-        fn(L, rank, size)
-        L.GA_Sync()
-        assert L.gaamd_ga_live_arrays() == live0, "a call left a global array alive"
-        print(f"SECTION {name} OK", flush=True)
-    sys.stdout.flush()
-    L.GA_Print_stats()
-    L.GA_Terminate()
-    print(f"RANK {rank} OK", flush=True)
-
-
 if __name__ == "__main__":
-    main()
+    run([("exact", exact), ("maps", maps), ("bits", bits)], aborts, check_live=True)

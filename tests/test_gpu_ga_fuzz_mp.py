@@ -14,77 +14,19 @@ matrix launch on as many ranks (profiles/r14/ga_fuzz/times.txt).
 
 Every rank process runs under its own time limit (a watcher thread each); once a launch ends in
 anything but the outcome its test expects, the remaining tests of this file start nothing."""
-import os
-import socket
-import subprocess
-import sys
-import threading
 import time
 
 import pytest
 
 import ga_fuzz_cases as F
+import mp_launch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-WORKER = os.path.join(HERE, "ga_fuzz_worker.py")
-
+MP = mp_launch.Launcher("ga_fuzz_worker.py", "z", marker="FUZZ FAILURE")
 # two launches per rank count, split by call family, so that each stays within the time of the
 # GA matrix launch on as many ranks (profiles/r14/ga_fuzz/times.txt)
 PARTS = {"math-elem-gemm": ("math", "elem", "gemm"), "trans-matrix-scan": ("trans", "matrix", "scan")}
 assert sorted(f for p in PARTS.values() for f in p) == sorted(F.FAMILIES)
-
-_broken = []
 _results = {}   # (part, rank count) -> the RESULT lines of its ranks
-
-
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def launch(n, limit=90, extra_env=None):
-    """[(exit status, output)] of the n ranks"""
-    if _broken:
-        pytest.fail(f"not started: an earlier launch of this file went wrong ({_broken[0]})")
-    port = str(free_port())
-    procs = []
-    for r in range(n):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(n), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=port, COMEX_AMD_JOBID=f"z{port}", COMEX_AMD_STAGING_MB="16",
-                   TEST_STACK_DUMP_S=str(limit - 15))
-        env.update(extra_env or {})
-        # the ranks are this process's own children: the node rendezvous is named after the
-        # parent's pid, so a wrapper process per rank would keep them from meeting
-        procs.append(subprocess.Popen([sys.executable, WORKER], cwd=ROOT, env=env, stdout=subprocess.PIPE,
-                                      stderr=subprocess.STDOUT, text=True))
-    res = [None] * n
-
-    def watch(r, p):   # each rank ends by itself or is killed at its own time limit
-        try:
-            out, _ = p.communicate(timeout=limit)
-            res[r] = (p.returncode, out)
-        except subprocess.TimeoutExpired:
-            p.kill()
-            out, _ = p.communicate()
-            res[r] = (124, out + f"\n[killed after {limit} s]")
-
-    watchers = [threading.Thread(target=watch, args=(r, p)) for r, p in enumerate(procs)]
-    for t in watchers:
-        t.start()
-    for t in watchers:
-        t.join()
-    return res
-
-
-def tails(res):
-    def tail(out):
-        i = out.find("FUZZ FAILURE")
-        return out[i:i + 3000] if i >= 0 else out[-2500:]
-    return "\n".join(f"--- rank {r}: status {rc} ---\n{tail(out)}" for r, (rc, out) in enumerate(res))
 
 
 @pytest.mark.gpu
@@ -97,13 +39,8 @@ def test_ga_fuzz_ranks(part, n):
     not depend on how the arrays are cut"""
     generated = sum(entry[0] in PARTS[part] for entry in F.PLAN)   # the plan is the list: one case per entry
     t0 = time.perf_counter()
-    res = launch(n, extra_env={"GA_FUZZ_FAMILIES": ",".join(PARTS[part])})
+    outs = MP.launch_ok(None, n, extra_env={"GA_FUZZ_FAMILIES": ",".join(PARTS[part])})
     took = time.perf_counter() - t0
-    for r, (rc, out) in enumerate(res):
-        if rc != 0 or f"RANK {r} OK" not in out:
-            _broken.append(f"{part} on {n} ranks: rank {r} status {rc}")
-            pytest.fail(f"rank {r} rc={rc}\n{tails(res)}")
-    outs = [out for _, out in res]
     ran = {int(ln.split()[1]) for out in outs for ln in out.splitlines() if ln.startswith("CASES ")}
     print(f"ga fuzz {part}: {n} ranks, {sorted(ran)} cases run of {generated} generated, {took:.2f} s")
     assert ran == {generated}

@@ -6,75 +6,12 @@ values: the numpy restatement in test_gpu_matrix.py, compared as raw bits by eve
 Every rank process runs under its own time limit (a watcher thread each); once a launch
 ends in anything but the outcome its test expects, the remaining tests of this file start
 nothing."""
-import os
-import socket
-import subprocess
-import sys
-import threading
-
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-WORKER = os.path.join(HERE, "ga_matrix_worker.py")
+import mp_launch
 
-_broken = []
+MP = mp_launch.Launcher("ga_matrix_worker.py", "m")
 _norms = {}   # rank count -> the NORM lines of its ranks
-
-
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def launch(mode, n, limit=90, extra_env=None):
-    """[(exit status, output)] of the n ranks"""
-    if _broken:
-        pytest.fail(f"not started: an earlier launch of this file went wrong ({_broken[0]})")
-    port = str(free_port())
-    procs = []
-    for r in range(n):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(n), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=port, COMEX_AMD_JOBID=f"m{port}", COMEX_AMD_STAGING_MB="16",
-                   TEST_STACK_DUMP_S=str(limit - 15))
-        env.update(extra_env or {})
-        # the ranks are this process's own children: the node rendezvous is named after the
-        # parent's pid, so a wrapper process per rank would keep them from meeting
-        procs.append(subprocess.Popen([sys.executable, WORKER, mode], cwd=ROOT, env=env, stdout=subprocess.PIPE,
-                                      stderr=subprocess.STDOUT, text=True))
-    res = [None] * n
-
-    def watch(r, p):   # each rank ends by itself or is killed at its own time limit
-        try:
-            out, _ = p.communicate(timeout=limit)
-            res[r] = (p.returncode, out)
-        except subprocess.TimeoutExpired:
-            p.kill()
-            out, _ = p.communicate()
-            res[r] = (124, out + f"\n[killed after {limit} s]")
-
-    watchers = [threading.Thread(target=watch, args=(r, p)) for r, p in enumerate(procs)]
-    for t in watchers:
-        t.start()
-    for t in watchers:
-        t.join()
-    return res
-
-
-def tails(res):
-    return "\n".join(f"--- rank {r}: status {rc} ---\n{out[-2500:]}" for r, (rc, out) in enumerate(res))
-
-
-def launch_ok(mode, n, **kw):
-    res = launch(mode, n, **kw)
-    for r, (rc, out) in enumerate(res):
-        if rc != 0 or f"RANK {r} OK" not in out:
-            _broken.append(f"{mode} on {n} ranks: rank {r} status {rc}")
-            pytest.fail(f"rank {r} rc={rc}\n{tails(res)}")
-    return [out for _, out in res]
 
 
 @pytest.mark.gpu
@@ -86,7 +23,7 @@ def test_ga_matrix_ranks(n):
     a 2-element vector of which one of three ranks owns nothing, the norms equal to the
     restatement on every rank count -- the same NORM lines on every rank and on every count --
     no temporary left behind, and the new statistics line beside the existing ones"""
-    outs = launch_ok("all", n)
+    outs = MP.launch_ok("all", n)
     for out in outs:
         for section in ("forms", "corners", "norms"):
             assert f"SECTION {section} OK" in out, out[-2000:]
@@ -110,10 +47,4 @@ def test_ga_scale_rows_wrong_length_aborts():
     """GA_Scale_rows with a g_v one element too long on 2 ranks: every rank prints the message
     and ends through GA_Error with a non-zero status, before the first sync: none is killed at its
     time limit and none reaches the line after the call"""
-    res = launch("abort-len", 2, limit=60)
-    for r, (rc, out) in enumerate(res):
-        ok = (rc not in (0, 3, 124, 137) and "ABORT EXPECTED" in out and "21 elements, 20 are needed" in out
-              and "NOT REACHED" not in out)
-        if not ok:
-            _broken.append(f"abort-len: rank {r} status {rc}")
-            pytest.fail(f"rank {r} rc={rc}\n{tails(res)}")
+    MP.expect_abort("abort-len", 2, ["21 elements, 20 are needed"])
