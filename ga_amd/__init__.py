@@ -371,6 +371,39 @@ def spmm_route_counts():
     return list(out)
 
 
+# Sparse x sparse at kernel level (gaamd_csr_rows / _spgemm_count / _spgemm_fill): A a block CSR as
+# above, B a row CSR -- brows + 1 long long offsets into rjdx / rval, row k being global row b_first + k.
+def spgemm_lds_cap():
+    """the largest product bound U of a row that takes the LDS hash-set path"""
+    return lib().gaamd_spgemm_lds_cap()
+
+
+def csr_rows(op, nrows, nblk, offs, start, jdx, val, roffs, rjdx, rval, stream=None):
+    """the block CSR flattened: roffs (nrows + 1 long long), rjdx, rval with every row's one list contiguous"""
+    return lib().gaamd_csr_rows(op, nrows, nblk, _vp(offs), _vp(start), _vp(jdx), _vp(val), _vp(roffs), _vp(rjdx),
+                                _vp(rval), stream)
+
+
+def spgemm_count(nrows, nblk, offs, start, jdx, b_first, brows, roffs, rjdx, jdim_c, ncut, counts, bound, stream=None):
+    """counts[b * nrows + r] = the distinct columns of row r of A B in column block b of ncut; bound[r] = its products"""
+    return lib().gaamd_spgemm_count(nrows, nblk, _vp(offs), _vp(start), _vp(jdx), b_first, brows, _vp(roffs), _vp(rjdx),
+                                    jdim_c, ncut, _vp(counts), _vp(bound), stream)
+
+
+def spgemm_fill(op, nrows, nblk, offs, start, jdx, val, b_first, brows, roffs, rjdx, rval, jdim_c, ncut, coffs, cstart,
+                cjdx, cval, stream=None):
+    """cjdx / cval of A B at cstart[b] + coffs[b][r], in the order contract of ga_amd.h"""
+    return lib().gaamd_spgemm_fill(op, nrows, nblk, _vp(offs), _vp(start), _vp(jdx), _vp(val), b_first, brows, _vp(roffs),
+                                   _vp(rjdx), _vp(rval), jdim_c, ncut, _vp(coffs), _vp(cstart), _vp(cjdx), _vp(cval), stream)
+
+
+def spgemm_route_counts():
+    """{B parts used in place, B parts copied} of NGA_Sprs_array_matmat_multiply so far"""
+    out = (ctypes.c_longlong * 2)()
+    lib().gaamd_ga_spgemm_route_counts(out)
+    return list(out)
+
+
 def sprs_range(dim, nproc, iproc):
     """(lo, hi) of the indices of a dimension of `dim` that rank iproc of nproc owns (host only)"""
     lo, hi = ctypes.c_long(0), ctypes.c_long(0)

@@ -2565,6 +2565,208 @@ int NGA_Sprs_array_create_from_sparse(int s_a) {
     return g_d;
 }
 
+// ---- sparse x sparse (sparse.array.c:2424-3103) ---------------------------------------------------
+// Rank l's row block of B is A's column block l: the cut rule is the same and B.idim == A.jdim.  Every
+// rank flattens its B into a row CSR (gaamd_csr_rows) inside a comex_malloc segment that lives for the
+// length of the call; a rank reads the parts its non-empty column blocks of A name with comex_get into
+// HBM scratch and runs gaamd_spgemm_count / _fill on its own rows.  No global array is created.
+static long g_spgemm_calls = 0;
+static long long g_spgemm_routes[2] = {0, 0};   // B parts used in place, B parts copied
+
+void gaamd_ga_spgemm_route_counts(long long counts[2]) { memcpy(counts, g_spgemm_routes, sizeof(g_spgemm_routes)); }
+
+// where rank p's part of B lies in its segment: (rows + 1) offsets, then jdx, then val from a 16-byte boundary
+struct SpgPart {
+    long long rows = 0, nnz = 0;
+    size_t jdx_at = 0, val_at = 0, bytes = 0;
+    SpgPart() {}
+    SpgPart(long long rows_, long long nnz_, int esz) : rows(rows_), nnz(nnz_) {
+        if (nnz == 0) return;   // nothing is published
+        jdx_at = (size_t)(rows + 1) * sizeof(long long);
+        val_at = (jdx_at + (size_t)nnz * sizeof(int) + 15) & ~(size_t)15;
+        bytes = val_at + (size_t)nnz * (size_t)esz;
+    }
+};
+
+// comex_get counts bytes in an int; the rank's own part is a local copy out of its segment
+static void spg_fetch(void *remote, void *local, size_t bytes, int proc, const char *what) {
+    if (proc == my_rank()) {
+        if (bytes && gaamd_memcpy(local, remote, bytes) != 0) fatal("%s: copying %zu bytes of this rank's part of B failed", what, bytes);
+        return;
+    }
+    const size_t piece = (size_t)1 << 30;
+    for (size_t k = 0; k < bytes; k += piece)
+        if (comex_get((char *)remote + k, (char *)local + k, (int)std::min(piece, bytes - k), proc, COMEX_GROUP_WORLD) !=
+            COMEX_SUCCESS)
+            fatal("%s: reading %zu bytes of rank %d's part of B failed", what, bytes, proc);
+}
+
+int NGA_Sprs_array_matmat_multiply(int s_a, int s_b) {
+    const char *what = "NGA_Sprs_array_matmat_multiply";
+    const int me = my_rank(), np = world_size();
+    SprsArray c;
+    {
+        const SprsArray &a = sprs_assembled(s_a, what), &b = sprs_assembled(s_b, what);
+        if (a.type != b.type) fatal("%s: the types of the two sparse arrays differ", what);
+        if (a.jdim != b.idim) fatal("%s: A has %ld columns, B has %ld rows", what, a.jdim, b.idim);
+        c.type = a.type;
+        c.elemsize = a.elemsize;
+        c.optype = a.optype;
+        c.idim = a.idim;
+        c.jdim = b.jdim;
+        c.ilo = a.ilo;
+        c.nrows = a.nrows;
+    }
+    const int esz = c.elemsize;
+    comex_barrier(COMEX_GROUP_WORLD);
+    g_spgemm_calls++;
+    // what every rank publishes
+    std::vector<long> nnzs((size_t)np, 0);
+    nnzs[(size_t)me] = (long)g_sprs[(size_t)s_b - 1].nnz;
+    exchange_slots(nnzs);
+    std::vector<SpgPart> parts((size_t)np);
+    std::vector<long long> row0((size_t)np + 1, 0);   // the first row of B of every rank
+    for (int p = 0; p < np; p++) {
+        long long lo, hi;
+        gaamd_sprs::range(g_sprs[(size_t)s_b - 1].idim, np, p, &lo, &hi);
+        row0[(size_t)p] = lo;
+        parts[(size_t)p] = SpgPart(hi - lo + 1, nnzs[(size_t)p], esz);
+    }
+    row0[(size_t)np] = g_sprs[(size_t)s_b - 1].idim;
+    std::vector<void *> seg((size_t)np, nullptr);
+    if (comex_malloc(seg.data(), parts[(size_t)me].bytes, COMEX_GROUP_WORLD) != COMEX_SUCCESS)
+        fatal("%s: no segment for %zu bytes of B", what, parts[(size_t)me].bytes);
+    const SpgPart &mine = parts[(size_t)me];
+    if (mine.bytes) {
+        const SprsArray &b = g_sprs[(size_t)s_b - 1];
+        if (gaamd_segment_kind(seg[(size_t)me]) == 2)
+            fatal("%s: segments live on the host (COMEX_AMD_SEGMENT=host); not supported", what);
+        char *sp = (char *)seg[(size_t)me];
+        launched(gaamd_csr_rows(b.optype, b.nrows, (int)b.blocks.size(), b.offs, b.dstart, b.jdx, b.val, (long long *)sp,
+                                (int *)(sp + mine.jdx_at), sp + mine.val_at, gaamd_stream()),
+                 what);
+        stream_wait(what);
+        g_stat.mathloc += 2.0 * (double)b.nnz * (esz + 4);
+    }
+    comex_barrier(COMEX_GROUP_WORLD);   // every part is published
+
+    const SprsArray a = g_sprs[(size_t)s_a - 1];   // the pointers are A's still: nothing is released here
+    std::vector<int> counts;   // [np][nrows]
+    Scratch g_offs, g_jdx, g_val, d_coffs, d_cstart;
+    const long long *roffs = nullptr;
+    const int *rjdx = nullptr;
+    const char *rval = nullptr;
+    long long b_first = 0, brows = 0;
+    if (a.nrows > 0 && !a.blocks.empty()) {
+        const int l0 = a.blocks.front(), l1 = a.blocks.back();
+        b_first = row0[(size_t)l0];
+        brows = (l1 + 1 < np ? row0[(size_t)l1 + 1] : row0[(size_t)np]) - b_first;
+        if (l0 == me && l1 == me && mine.bytes) {   // its own part alone: in place
+            const char *sp = (const char *)seg[(size_t)me];
+            roffs = (const long long *)sp;
+            rjdx = (const int *)(sp + mine.jdx_at);
+            rval = sp + mine.val_at;
+            g_spgemm_routes[0]++;
+        } else {   // one row CSR over the span; the blocks A does not name, and the parts without entries, give empty rows
+            long long total = 0;
+            for (int l : a.blocks) total += parts[(size_t)l].nnz;
+            std::vector<long long> offs((size_t)brows + 1, 0);
+            if (!g_offs.alloc(offs.size() * sizeof(long long)) || !g_jdx.alloc(std::max<size_t>(16, (size_t)total * sizeof(int))) ||
+                !g_val.alloc(std::max<size_t>(16, (size_t)total * (size_t)esz)))
+                fatal("%s: no device memory for %lld gathered entries of B", what, total);
+            long long at = 0;
+            size_t r = 0;
+            for (int l = l0; l <= l1; l++) {
+                const SpgPart &p = parts[(size_t)l];
+                const bool named = std::binary_search(a.blocks.begin(), a.blocks.end(), l) && p.nnz > 0;
+                if (named) {
+                    std::vector<long long> theirs((size_t)p.rows + 1);
+                    spg_fetch(seg[(size_t)l], theirs.data(), theirs.size() * sizeof(long long), l, what);
+                    for (long long q = 0; q < p.rows; q++) offs[r + (size_t)q] = at + theirs[(size_t)q];
+                    spg_fetch((char *)seg[(size_t)l] + p.jdx_at, (int *)g_jdx.p + at, (size_t)p.nnz * sizeof(int), l, what);
+                    spg_fetch((char *)seg[(size_t)l] + p.val_at, (char *)g_val.p + at * esz, (size_t)p.nnz * (size_t)esz, l, what);
+                    at += p.nnz;
+                    g_spgemm_routes[1]++;
+                } else {
+                    for (long long q = 0; q < p.rows; q++) offs[r + (size_t)q] = at;
+                }
+                r += (size_t)p.rows;
+            }
+            offs[(size_t)brows] = at;
+            if (gaamd_memcpy(g_offs.p, offs.data(), offs.size() * sizeof(long long)) != 0) fatal("%s: copying the offsets failed", what);
+            roffs = (const long long *)g_offs.p;
+            rjdx = (const int *)g_jdx.p;
+            rval = (const char *)g_val.p;
+            g_stat.mathloc += (double)total * (esz + 4);
+        }
+        // the counting phase
+        Scratch d_counts, d_bound;
+        counts.resize((size_t)np * (size_t)a.nrows);
+        if (!d_counts.alloc(counts.size() * sizeof(int)) || !d_bound.alloc((size_t)a.nrows * sizeof(long long)))
+            fatal("%s: no device memory for the counts of %lld rows", what, a.nrows);
+        launched(gaamd_spgemm_count(a.nrows, (int)a.blocks.size(), a.offs, a.dstart, a.jdx, b_first, brows, roffs, rjdx, c.jdim,
+                                    np, (int *)d_counts.p, (long long *)d_bound.p, gaamd_stream()),
+                 what);
+        stream_wait(what);
+        if (gaamd_memcpy(counts.data(), d_counts.p, counts.size() * sizeof(int)) != 0) fatal("%s: reading the counts failed", what);
+    }
+    // per block: the offsets of the rows and the total; the 2^31 check on the table of all ranks
+    std::vector<int> coffs((size_t)np * (size_t)(c.nrows + 1), 0);
+    std::vector<long long> cstart((size_t)np, 0);
+    long long held = 0;
+    for (int b = 0; b < np; b++) {
+        cstart[(size_t)b] = held;
+        long long run = 0;
+        int *o = coffs.data() + (size_t)b * (size_t)(c.nrows + 1);
+        for (long long r = 0; r < c.nrows; r++) {
+            o[r] = (int)std::min<long long>(run, INT32_MAX);
+            if (!counts.empty()) run += counts[(size_t)b * (size_t)c.nrows + (size_t)r];
+        }
+        o[c.nrows] = (int)std::min<long long>(run, INT32_MAX);
+        held += run;
+    }
+    std::vector<long> totals((size_t)np, 0);
+    totals[(size_t)me] = (long)held;
+    exchange_slots(totals);
+    for (int p = 0; p < np; p++) {   // every rank holds the totals: all end here, before anything is stored
+        if (totals[(size_t)p] >= (1l << 31)) fatal("%s: rank %d would hold %ld entries, 2^31 or more", what, p, totals[(size_t)p]);
+        c.nnz_total += totals[(size_t)p];
+    }
+    c.nnz = held;
+    c.team = gaamd_spmv_team(c.nnz_total, c.idim);
+    if (held > 0) {
+        c.jdx = (int *)sprs_dev_alloc((size_t)held * sizeof(int), what);
+        c.val = (char *)sprs_dev_alloc((size_t)held * (size_t)esz, what);
+        if (!d_coffs.alloc(coffs.size() * sizeof(int)) || !d_cstart.alloc(cstart.size() * sizeof(long long)))
+            fatal("%s: no device memory for the offsets of %lld rows", what, c.nrows);
+        if (gaamd_memcpy(d_coffs.p, coffs.data(), coffs.size() * sizeof(int)) != 0 ||
+            gaamd_memcpy(d_cstart.p, cstart.data(), cstart.size() * sizeof(long long)) != 0)
+            fatal("%s: copying the offsets failed", what);
+        launched(gaamd_spgemm_fill(a.optype, a.nrows, (int)a.blocks.size(), a.offs, a.dstart, a.jdx, a.val, b_first, brows, roffs,
+                                   rjdx, rval, c.jdim, np, (const int *)d_coffs.p, (const long long *)d_cstart.p, c.jdx, c.val,
+                                   gaamd_stream()),
+                 what);
+        // the empty blocks are dropped: what stays is assemble's layout
+        std::vector<int> offs;
+        for (int b = 0; b < np; b++) {
+            const int *o = coffs.data() + (size_t)b * (size_t)(c.nrows + 1);
+            if (o[c.nrows] == 0) continue;
+            c.blocks.push_back(b);
+            c.start.push_back(cstart[(size_t)b]);
+            offs.insert(offs.end(), o, o + c.nrows + 1);
+        }
+        c.offs = (int *)sprs_upload(offs.data(), offs.size() * sizeof(int), what);
+        c.dstart = (long long *)sprs_upload(c.start.data(), c.start.size() * sizeof(long long), what);
+        g_stat.mathloc += (double)held * (esz + 4) + (double)a.nnz * (esz + 4);
+    }
+    c.live = true;
+    c.assembled = true;
+    math_end(what);   // every rank is done reading the parts
+    comex_free(seg[(size_t)me], COMEX_GROUP_WORLD);
+    g_sprs.push_back(c);
+    return (int)g_sprs.size();
+}
+
 void GA_Print_stats(void) {
     printf("[%d] GA on-device calls: fill %ld, scale %ld, add %ld, copy %ld, dot %ld; local bytes moved %.0f; "
            "gemm %ld\n",
@@ -2591,6 +2793,7 @@ void GA_Print_stats(void) {
            g_stat.numsprs[SP_DIAG_RIGHT]);
     printf("[%d] GA sparse-product calls: sprsdns %ld, from_dense %ld, from_sparse %ld\n", my_rank(),
            g_spmm_calls[SM_SPRSDNS], g_spmm_calls[SM_FROM_DENSE], g_spmm_calls[SM_FROM_SPARSE]);
+    if (g_spgemm_calls > 0) printf("[%d] GA sparse-sparse calls: matmat %ld\n", my_rank(), g_spgemm_calls);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include "gaamd_scan.hip"
 #include "gaamd_sprs.hip"
 #include "gaamd_spmm.hip"
+#include "gaamd_spgemm.hip"
 #include "gaamd_gemm.hip"
 #include "gaamd_gemm_cplx.hip"
 #include "gaamd_transpose.hip"

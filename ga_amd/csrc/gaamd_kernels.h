@@ -204,6 +204,18 @@ int launch_dense_csr(int op, long long rows, long long cols, const void *a, long
                      hipStream_t stream);
 int launch_csr_to_dense(int op, long long nrows, long long cols, const int *offs, const int *jdx, const void *val,
                         long long col_first, void *out, long long ldo, hipStream_t stream);
+// ---- sparse x sparse (gaamd_spgemm.hip; ga_amd.h gaamd_csr_rows / _spgemm_count / _spgemm_fill): A the block CSR
+// above, B a row CSR (brows + 1 64-bit offsets, jdx, val) of the global rows b_first ..; the codes are the patch codes ----
+int spgemm_lds_cap();
+int launch_csr_rows(int op, long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+                    const void *val, long long *roffs, int *rjdx, void *rval, hipStream_t stream);
+int launch_spgemm_count(long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+                        long long b_first, long long brows, const long long *roffs, const int *rjdx, long long jdim_c,
+                        int ncut, int *counts, long long *bound, hipStream_t stream);
+int launch_spgemm_fill(int op, long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+                       const void *val, long long b_first, long long brows, const long long *roffs, const int *rjdx,
+                       const void *rval, long long jdim_c, int ncut, const int *coffs, const long long *cstart, int *cjdx,
+                       void *cval, hipStream_t stream);
 struct PatchPlan;
 // launch_patch_add's checks without a launch (no device): 0 launch, 1 nothing to do, < 0 error;
 // plan[0..3] = {vector width, row levels after merging, rows, vectors per row}

@@ -209,6 +209,28 @@ int gaamd_csr_to_dense(int op, long long nrows, long long cols, const int *offs,
     return launch_csr_to_dense(op, nrows, cols, offs, jdx, val, col_first, out, ldo, stream_of(stream));
 }
 
+int gaamd_spgemm_lds_cap(void) { return spgemm_lds_cap(); }
+
+int gaamd_csr_rows(int op, long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+                   const void *val, long long *roffs, int *rjdx, void *rval, void *stream) {
+    return launch_csr_rows(op, nrows, nblk, offs, start, jdx, val, roffs, rjdx, rval, stream_of(stream));
+}
+
+int gaamd_spgemm_count(long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+                       long long b_first, long long brows, const long long *roffs, const int *rjdx, long long jdim_c,
+                       int ncut, int *counts, long long *bound, void *stream) {
+    return launch_spgemm_count(nrows, nblk, offs, start, jdx, b_first, brows, roffs, rjdx, jdim_c, ncut, counts, bound,
+                               stream_of(stream));
+}
+
+int gaamd_spgemm_fill(int op, long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+                      const void *val, long long b_first, long long brows, const long long *roffs, const int *rjdx,
+                      const void *rval, long long jdim_c, int ncut, const int *coffs, const long long *cstart, int *cjdx,
+                      void *cval, void *stream) {
+    return launch_spgemm_fill(op, nrows, nblk, offs, start, jdx, val, b_first, brows, roffs, rjdx, rval, jdim_c, ncut, coffs,
+                              cstart, cjdx, cval, stream_of(stream));
+}
+
 int gaamd_gemm(int op, int transa, int transb, long long m, long long n, long long k, const void *alpha,
                const void *a, long long lda, const void *b, long long ldb, const void *beta, void *c, long long ldc,
                void *stream) {

@@ -431,9 +431,46 @@ void GA_Unpack(int g_src, int g_dst, int g_msk, int lo, int hi, int *icount);
    is not live or not assembled; an array of rank other than 2; a type that differs; g_b with other
    than jdim rows; an array in a host segment.  A rank that would keep 2^31 entries or more ends
    create_from_dense on every rank, after the counting launch and before anything is stored.
-   Not provided: the *64 forms, matmat_multiply, dnssprs_multiply (it needs every rank to read the
-   other ranks' CSR blocks, i.e. get_block), get_block, get_column, export, count_sketch; assembly
-   still sorts on the host. */
+   Sparse x sparse (sparse.array.c:2424-3103), collective:
+     s_c = NGA_Sprs_array_matmat_multiply(s_a, s_b)       a NEW assembled sparse array C = A B
+   of A.idim x B.jdim and the operands' type, on A's row cuts; s_a == s_b is allowed; A and B are
+   unchanged; gaamd_ga_live_arrays() is the same before and after the call; C is the caller's to
+   destroy.  Structure: C holds exactly one entry for every (i, j) for which some k has a stored
+   A(i,k) and a stored B(k,j).  Nothing is dropped for being numerically zero: a product of 0, or a
+   sum that cancels, keeps its entry (the reference tests existence, never value).  The entries of a
+   row are in ascending column order, the column blocks those of owner(j, B.jdim, nproc), and the
+   stored layout is bit for bit what NGA_Sprs_array_create, add_element of C's (i, j, value)
+   triples and assemble give: the non-empty block list, the starts, the per-block offset tables,
+   jdx, val, the entry counts and the team gaamd_spmv_team(entries of C, idim).  Every call above
+   therefore works on C without knowing where it came from.
+   Arithmetic contract: gaamd_spgemm_fill's (ga_amd.h) -- c_ij starts from +0 and takes one product
+   and then one add per contributing pair, never fused; the order is A's row-i list as ONE list over
+   its column blocks ascending, duplicates in storage order, and for each A entry with column k B's
+   row-k ONE list in storage order, restricted to column j; the true complex product; integers wrap.
+   So C is the same bits on every call and on any rank count whenever the operands' duplicates keep
+   their relative order.  One stated departure: the reference ASSIGNS the first product where this
+   ADDS it to +0; the two differ only for a lone -0.0 product.  With the +0 start, for finite data
+   and a B without duplicates, create_from_sparse(A B) equals
+   sprsdns_multiply(A, create_from_sparse(B)) bit for bit.
+   How: rank l's row block of B is A's column block l (the same cut rule, B.idim == A.jdim).  Every
+   rank flattens its B into a row CSR (gaamd_csr_rows) inside a comex_malloc segment that is freed
+   before the call returns; no global array is created.  A rank gathers the parts named by its
+   non-empty column blocks of A with comex_get into ONE row CSR in HBM scratch over its column span
+   (blocks in between, and parts without entries, give empty rows); where the only part named is
+   its own, that part is used where it lies, without a copy (in practice the one-rank route, or a
+   block-diagonal A); otherwise its own part is copied into the gathered CSR device to device.
+   Then gaamd_spgemm_count, the exchange
+   of the ranks' totals, allocation, gaamd_spgemm_fill, and the empty blocks are dropped.  A rank
+   without rows launches nothing of these and takes part in every sync.  A LIMIT: a rank may hold a
+   copy of all of B (the reference's get_block loop fetches the same); B is not panelled.
+   gaamd_ga_spgemm_route_counts: {B parts used in place, B parts copied into the gathered CSR} on
+   this rank so far.  The call does not count as an assemble; GA_Print_stats prints the line
+   "GA sparse-sparse calls: matmat N" once it has been made.
+   It aborts through GA_Error on every rank before the first sync or launch: a handle that is not
+   live or not assembled; types that differ; A.jdim != B.idim.  After the counting phase and before
+   anything is stored, a rank that would hold 2^31 entries of C or more ends every rank.
+   Not provided: the *64 forms, dnssprs_multiply, get_block, get_column (they need the CSR
+   persistently remote-readable), export, count_sketch; assembly still sorts on the host. */
 int NGA_Sprs_array_create(int idim, int jdim, int type);
 void NGA_Sprs_array_add_element(int s_a, int idx, int jdx, void *val);
 int NGA_Sprs_array_assemble(int s_a);
@@ -455,6 +492,8 @@ int NGA_Sprs_array_sprsdns_multiply(int s_a, int g_b);
 int NGA_Sprs_array_create_from_dense(int g_a);
 int NGA_Sprs_array_create_from_sparse(int s_a);
 void gaamd_ga_spmm_route_counts(long long counts[4]);
+int NGA_Sprs_array_matmat_multiply(int s_a, int s_b);
+void gaamd_ga_spgemm_route_counts(long long counts[2]);
 /* global arrays alive on this rank (temporaries of the general path are destroyed
    before their call returns) */
 int gaamd_ga_live_arrays(void);

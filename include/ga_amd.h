@@ -393,6 +393,68 @@ int gaamd_dense_to_csr(int op, long long rows, long long cols, const void *a, lo
                        long long col_first, const int *offs, int *jdx, void *val, void *stream);
 int gaamd_csr_to_dense(int op, long long nrows, long long cols, const int *offs, const int *jdx, const void *val,
                        long long col_first, void *out, long long ldo, void *stream);
+/* Sparse x sparse, C = A B with all three sparse (sparse.array.c:2424-3103); the kernels under
+ * NGA_Sprs_array_matmat_multiply (ga.h).  All six types, all addresses HBM.  A is the block CSR of
+ * gaamd_spmv.  B is a ROW CSR: brows + 1 offsets (long long) into rjdx (int, global columns) / rval,
+ * row k of it being global row b_first + k of B, each row's entries its ONE list; the entries of A
+ * name rows in [b_first, b_first + brows).  Offsets are 64-bit because a gathered B may exceed 2^31
+ * entries although no rank's part does.
+ * REQUIRED of the caller of gaamd_spgemm_count and gaamd_spgemm_fill, and checked by neither (the
+ * arrays lie in HBM): (1) every row of the row CSR is in ascending column order, so that duplicates
+ * of one (k, j) lie side by side -- what gaamd_csr_rows gives from an assembled block CSR; otherwise
+ * two lanes add onto one value at once and the result is undefined; (2) every jdx of A lies in
+ * [b_first, b_first + brows); otherwise roffs is read out of bounds; (3) coffs / cstart are the
+ * prefix sums of the counts gaamd_spgemm_count gave for the same operands.
+ *   gaamd_csr_rows   flattens a block CSR into the row CSR of the same nrows rows: roffs (nrows + 1),
+ *                rjdx and rval (as many entries as the block CSR holds), every row's one list
+ *                contiguous, the blocks ascending, storage order kept: row lengths over the blocks,
+ *                a prefix sum, a copy.  With nblk == 0, roffs becomes nrows + 1 zeros.
+ *   gaamd_spgemm_count   counts[b * nrows + r] = the DISTINCT columns j of row r of C that lie in
+ *                column block b of ncut, a column j of jdim_c belonging to block
+ *                min(j * ncut / jdim_c, ncut - 1); every one of the ncut blocks has its nrows counts,
+ *                an empty one zeros.  bound[r] = U[r] = the sum of the lengths of the rows of B that
+ *                row r's entries name, duplicates counted: the products of the row.
+ *   gaamd_spgemm_fill    given coffs, the [ncut][nrows + 1] exclusive prefix sums of those counts per
+ *                block, and cstart[ncut], where each block begins in cjdx / cval (both HBM): the
+ *                columns of row r in block b go to cjdx at cstart[b] + coffs[b][r] .., ascending,
+ *                their values to cval.  cstart[b] + coffs[b][nrows] is below 2^31 for every b.
+ * Structure: C holds exactly one entry per (r, j) for which some k has a stored a_rk and a stored
+ * b_kj; existence only is tested, never a value, so a product of 0 or a sum that cancels keeps its
+ * entry.
+ * Arithmetic and order (a contract, as gaamd_spmm's): c_rj starts from +0 and takes one product and
+ * then one add per contributing pair, never fused.  The order: A's row-r list as ONE list over its
+ * column blocks ascending, duplicates in storage order; for each A entry with column k, B's row-k
+ * list in storage order, restricted to column j.  A complex product is the true product, part by
+ * part; integers wrap.  One stated departure: the reference ASSIGNS the first product where this
+ * ADDS it to +0; the two differ only for a lone -0.0 product.  With that start, for finite data
+ * and a B without duplicates, the dense copy of C equals gaamd_spmm of A with the dense copy of B
+ * bit for bit.  The bits depend neither on the grid nor on the path a row takes.
+ * Shape: one wave per row.  A row with U <= gaamd_spgemm_lds_cap() (1024) collects its columns in
+ * an LDS hash set (integer compare-and-swap on the key only), compacts and bitonic-sorts it; the
+ * cuts are found by binary search.  A larger row takes its column blocks in windows of 32768
+ * columns marked in an LDS bitmap, walking its products once per window: the same bits, not fast.
+ * Fill walks A's row list sequentially with the lanes along B's row; duplicates (k, j) lie side by
+ * side in B's row, only the head of a run acts and adds its run in order, so a place has one writer
+ * per A entry: plain loads and stores, no floating-point atomics.  8 KiB of LDS per wave (20 waves
+ * per CU), no scratch memory, no HBM scratch; every index into every array is 64-bit.
+ * Negative codes, all before any launch, in this order: -3 a negative nrows, nblk, brows, jdim_c or
+ * ncut; -4 an unknown op (csr_rows, fill); then nrows == 0 (count, fill: or ncut == 0): 0 and no
+ * launch; -5 a missing pointer (with nblk == 0 the outputs only -- roffs; counts and bound; coffs,
+ * cstart, cjdx, cval); -7 nrows or brows above 2^40, jdim_c outside 1 .. 2^31 - 1, a negative
+ * b_first (ncut may exceed jdim_c: blocks without columns stay empty); -8 val, rval or cval below
+ * the element's alignment, start, roffs, cstart or bound below 8, offs, jdx, rjdx, coffs, counts or
+ * cjdx below 4; -11 an output overlaps an input (a length that is no argument is stood for by the
+ * first entry). */
+int gaamd_spgemm_lds_cap(void);
+int gaamd_csr_rows(int op, long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+                   const void *val, long long *roffs, int *rjdx, void *rval, void *stream);
+int gaamd_spgemm_count(long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+                       long long b_first, long long brows, const long long *roffs, const int *rjdx, long long jdim_c,
+                       int ncut, int *counts, long long *bound, void *stream);
+int gaamd_spgemm_fill(int op, long long nrows, int nblk, const int *offs, const long long *start, const int *jdx,
+                      const void *val, long long b_first, long long brows, const long long *roffs, const int *rjdx,
+                      const void *rval, long long jdim_c, int ncut, const int *coffs, const long long *cstart, int *cjdx,
+                      void *cval, void *stream);
 /* Row-major GEMM on the gfx950 matrix cores, for op = COMEX_ACC_DBL (v_mfma_f64_16x16x4_f64)
  * and COMEX_ACC_FLT (v_mfma_f32_16x16x4_f32); the kernel under GA_Dgemm / GA_Sgemm (ga.h):
  *   C[i][j] = alpha * sum_k op(A)[i][k] * op(B)[k][j] + beta * C[i][j],  i < m, j < n, kk < k
